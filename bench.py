@@ -23,6 +23,11 @@ One step = the whole hot path over the rank's corpus, inputs resident in HBM:
 
 Launched as `python bench.py` (N=1) or under torch.distributed.run for N>1
 (RANK/LOCAL_RANK/WORLD_SIZE from the env, backend nccl = RCCL).
+
+A plain run does only what the headline figure needs: generate and load the corpus, warm up, time the
+steps (no HIP events in them), write the last step's results (--dump-outputs) and print the result line.
+--full adds every other leg: the per-kernel table and the dominant kernel's roofline (--kernel-timing),
+the per-run diff roofline (--diff-reps), the end-to-end ingest leg (--e2e-runs) and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -32,6 +37,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -91,7 +97,20 @@ def parse():
     ap.add_argument("--diff-reps", type=int, default=5,
                     help="per_run differential-provenance leg after the timed steps (roofline_diff): this many "
                          "nemo_diffprov(failed, NEMO_DIFF_PER_RUN) calls over the resident corpus (0: off)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the timed steps: the kernel table and the roofline (--kernel-timing), the "
+                         "per-run diff roofline (--diff-reps), the end-to-end leg (--e2e-runs) and the CPU baseline "
+                         "(--no-cpu-baseline, --cpu-seconds); without it those options have no effect and their "
+                         "result fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step handed to the host as "
+                         "DIR/<name>.npy (float32 / float64): node state, chain pairs, D masks, missing events, "
+                         "prototypes, table sets, missingFrom sets, trigger rows; an array over the per-file budget "
+                         "is a fixed, seeded sample of its elements (under 64 MB in all)")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and nothing beside them
+        args.no_cpu_baseline, args.e2e_runs, args.diff_reps, args.kernel_timing = True, 0, 0, "none"
+    return args
 
 
 # workload per config (generator settings: tools/synth.py CONFIGS); cpu_runs: the bounded sample the CPU
@@ -262,16 +281,18 @@ def main():
         eng.pull(2)
         protos = eng.protos_finalize(d_red.data_ptr())
         tabs = eng.run_tables(1)
+        mi = mu = trig = None
         if len(fidx):  # missingFrom (prototype.go:141-206) for every failed run: proto tables absent from its set
             tf = tabs[fidx]
-            _ = table_mask(protos["inter"], tf.shape[1]) & ~tf
-            _ = table_mask(protos["union"], tf.shape[1]) & ~tf
+            mi = table_mask(protos["inter"], tf.shape[1]) & ~tf
+            mu = table_mask(protos["union"], tf.shape[1]) & ~tf
         if has_run0:
-            eng.trigger_rows()
+            trig = eng.trigger_rows()
         masks = eng.diff_masks_view() if failed else None
         miss = eng.missing()
         state, chain_off, chain_ht = eng.simplified_view()
-        return state, chain_off, chain_ht, masks, miss
+        return {"state": state, "chain_off": chain_off, "chain_ht": chain_ht, "masks": masks, "missing": miss,
+                "protos": protos, "tables": tabs, "missing_inter": mi, "missing_union": mu, "triggers": trig}
 
     if lanes_n > 1:
         step = lambda: step_lanes(lanes, corpus, mode)  # noqa: E731
@@ -301,7 +322,7 @@ def main():
         warm = gather_timings()
     dom_group = max(warm.items(), key=lambda kv: kv[1]["ms"])[0] if warm else None
     for e in engines:
-        e.set_timing(args.kernel_timing != "off")
+        e.set_timing(args.kernel_timing in ("dominant", "on"))
         e.set_timing_groups([dom_group] if dom_group else [])
         e.reset_timings()
     if world > 1:
@@ -313,8 +334,9 @@ def main():
     gc.disable()
     t_start = time.perf_counter()
     step_ends = []
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
         step_ends.append(time.perf_counter())
     if world > 1:
         dist.barrier()
@@ -322,6 +344,18 @@ def main():
     elapsed = time.perf_counter() - t_start
     gc.enable()
     step_ms = [round((b - a) * 1e3, 3) for a, b in zip([t_start] + step_ends[:-1], step_ends)]
+    if args.dump_outputs and rank == 0:  # before any further leg reuses the staged views
+        if last is None:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        V = int(corpus.node_off[-1])
+        if lanes_n > 1:
+            named = {}
+            for k, (ln, (simp, masks, miss)) in enumerate(zip(lanes, last)):
+                o = {"state": simp[0], "chain_off": simp[1], "chain_ht": simp[2], "masks": masks, "missing": miss}
+                named.update({f"lane{k}_{n}": a for n, a in named_outputs(o, int(ln["corpus"].node_off[-1])).items()})
+        else:
+            named = named_outputs(last, V)
+        dump_outputs(args.dump_outputs, named)
     if args.kernel_timing == "off":
         for e in engines:
             e.set_timing(True)
@@ -353,12 +387,17 @@ def main():
         edges = float(t.item())
     # edges/s: edges examined by all traversal kernels of all ranks over the wall time
     edges_per_s = edges / elapsed
-    dname = dom_group or max(tim.items(), key=lambda kv: kv[1]["ms"])[0]
-    d = tim[dname]
-    per_launch_bytes = d["bytes"] / d["launches"]
-    avg_ms = d["ms"] / d["launches"]
-    achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
-    traffic = pmc_traffic(dname, corpus)
+    roofline = None
+    if tim:
+        dname = dom_group or max(tim.items(), key=lambda kv: kv[1]["ms"])[0]
+        d = tim[dname]
+        per_launch_bytes = d["bytes"] / d["launches"]
+        avg_ms = d["ms"] / d["launches"]
+        achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "kernel": dname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(dname, corpus),
+                    "bytes_per_launch": per_launch_bytes, "avg_launch_ms": round(avg_ms, 4),
+                    "bytes_formula": "DESIGN.md section 3 (HBM lower bound per launch)"}
     rdiff = None
     if args.diff_reps > 0 and lanes_n == 1:
         rdiff = diff_leg(args, eng, corpus, failed, world, torch, dist)
@@ -404,17 +443,18 @@ def main():
                                      "contexts, one stream each, phases issued in turn, vectors summed on the "
                                      "host" if lanes_n > 1 else ""),
                    "lib_options": args.set},
-        "edges_traversed_per_s": round(edges_per_s, 1),
-        "roofline": {"bound": "hbm", "kernel": dname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "bytes_per_launch": per_launch_bytes, "avg_launch_ms": round(avg_ms, 4),
-                     "bytes_formula": "DESIGN.md section 3 (HBM lower bound per launch)"},
+        "full": args.full,
+        # the traversed edges are the library's per-launch counts: null without its timing table (--full)
+        "edges_traversed_per_s": round(edges_per_s, 1) if table else None,
+        "roofline": roofline,
         "cpu_baseline": cpu,
         "kernels": {k: {"launches": v["launches"], "ms_total": round(v["ms"], 3),
                         "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
-                    for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms"])},
-        "kernel_timing": {"mode": args.kernel_timing, "timed_steps_groups": [dom_group] if dom_group else "all",
-                          "kernels_table_from": "one untimed step after the warmup" if dom_group else "the timed steps"},
+                    for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms"])} if table else None,
+        "kernel_timing": {"mode": args.kernel_timing,
+                          "timed_steps_groups": ([dom_group] if dom_group else "all") if tim else [],
+                          "kernels_table_from": None if not table else "one untimed step after the warmup"
+                                                if dom_group else "the timed steps"},
         "step_host_ms_rank0": step_ms,
         "gen_seconds_rank0": round(gen_s, 2),
         "hbm_used_gb_rank0": round(hbm_used / 1e9, 2),
@@ -447,6 +487,58 @@ def table_mask(tables, words):
     for t in tables:
         m[t >> 5] |= np.uint32(1 << (t & 31))
     return m
+
+
+DUMP_SEED = 0x6E656D6F       # the samples' seed: fixed, so that two builds dump the same elements
+DUMP_BYTES = 60_000_000      # all files of a dump together (the budget is shared evenly by the arrays)
+
+
+def named_outputs(o, V):
+    """--dump-outputs: a step's host-facing results by name.  Packed results are (words, bits per element,
+    elements) and are dumped element by element: the 2-bit node state (alive | holds << 1) per node, table
+    bitsets per (run, table)."""
+    def bitset(w):
+        return (w, 1, w.size * 32)
+    out = {"node_state": (o["state"], 2, V), "chain_off": o["chain_off"], "chain_ht": o["chain_ht"],
+           "missing_events": o["missing"]}
+    if o["masks"] is not None:
+        out["diff_masks"] = o["masks"]
+    if o.get("protos") is not None:
+        p = o["protos"]
+        out["proto_inter"] = np.array(p["inter"], np.uint32)
+        out["proto_union"] = np.array(p["union"], np.uint32)
+        out["proto_scalars"] = np.array([p["achieved"], p["pre_holds"], p["n_runs"]], np.uint64)
+        out["run_tables"] = bitset(o["tables"])
+    if o.get("missing_inter") is not None:
+        out["missing_inter"] = bitset(o["missing_inter"])
+        out["missing_union"] = bitset(o["missing_union"])
+    if o.get("triggers") is not None:
+        pre, post, asy = o["triggers"]
+        out.update({"trigger_pre": pre, "trigger_post": post, "trigger_async": np.sort(asy)})  # async: a set
+    return out
+
+
+def dump_outputs(path, named):
+    """Every named array as path/<name>.npy: float32 where that is exact (<= 16-bit values), else float64 (exact
+    for the u32 / u64 values here).  An array of more elements than its share of DUMP_BYTES is a sample: sorted
+    element indices drawn with a generator seeded by DUMP_SEED and the name, the same from run to run."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // (8 * max(len(named), 1))
+    for name, a in named.items():
+        packed = isinstance(a, tuple)
+        words, bits, n = a if packed else (np.asarray(a), 0, np.asarray(a).size)
+        shape, words = words.shape, words.reshape(-1)
+        idx = None
+        if n > cap:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())]).integers(0, n, cap))
+        if packed:
+            i = np.arange(n, dtype=np.int64) if idx is None else idx
+            per = words.itemsize * 8 // bits
+            v = (words[i // per].astype(np.uint32) >> ((i % per) * bits).astype(np.uint32)) & np.uint32((1 << bits) - 1)
+        else:
+            v = words.reshape(shape) if idx is None else words[idx]
+        np.save(os.path.join(path, name + ".npy"),
+                np.asarray(v, np.float32 if packed or v.dtype.itemsize <= 2 else np.float64))
 
 
 def runs_total_main(args, cfg, gen, threads, world, rank, local, torch, dist):
@@ -494,8 +586,10 @@ def runs_total_main(args, cfg, gen, threads, world, rank, local, torch, dist):
             dist.barrier()
         torch.cuda.synchronize()
         t_start = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            phase = bp.run_pass().phases
+            last = bp.run_pass()
+            phase = last.phases
         bp.drain()  # the next pass's first load, started inside the timed passes, is timed too
         if world > 1:
             dist.barrier()
@@ -503,6 +597,13 @@ def runs_total_main(args, cfg, gen, threads, world, rank, local, torch, dist):
         elapsed = time.perf_counter() - t_start
     finally:
         bp.close()
+    if args.dump_outputs and rank == 0:  # what a timed pass returns: the cross-batch prototype results
+        if last is None:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        dump_outputs(args.dump_outputs, {"proto_inter": np.array(last.inter, np.uint32),
+                                         "proto_union": np.array(last.union, np.uint32),
+                                         "proto_achieved": np.array([last.achieved], np.uint32),
+                                         "reduce_vector": last.vec})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -526,6 +627,7 @@ def runs_total_main(args, cfg, gen, threads, world, rank, local, torch, dist):
     out = {"metric": METRIC, "value": round(total * args.steps / elapsed, 2), "unit": "runs/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+           "full": args.full,
            "config": {"workload": "C5 at its configured size: runs_total runs x (pre, post) graphs of ~nodes_per_graph "
                                   "nodes / ~4 edges per node at EOT eot (BASELINE configs[4]); a step is one pass "
                                   "over every run, batches of batch_runs uploaded on one context while the previous "

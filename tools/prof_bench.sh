@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile of bench.py on the GPU box (run under gpurun):
-#   1. bench.py as the driver runs it                       -> bench.json
+#   1. bench.py --full (every leg of the result line)       -> bench.json
 #   2. the same command under rocprofv3 --kernel-trace --stats -> trace/
 #   3. separate PMC passes (HBM bytes, SQ occupancy/stalls)   -> pmc_*/
 # tools/pmc_summary.py turns the CSVs into profiles/.
@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/prof_${1:-run}
 shift || true
 mkdir -p $OUT
 cd $R
-timeout -k 10 600 python3 bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python3 bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o kt --output-format csv -- python3 bench.py --no-cpu-baseline --e2e-runs 0 "$@" > $OUT/trace.log 2>&1
 timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f --output-format csv -- python3 bench.py --steps 2 --warmup 0 --no-cpu-baseline --e2e-runs 0 "$@" > $OUT/pmc_fetch.log 2>&1
 timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o w --output-format csv -- python3 bench.py --steps 2 --warmup 0 --no-cpu-baseline --e2e-runs 0 "$@" > $OUT/pmc_write.log 2>&1
