@@ -98,10 +98,12 @@ typedef struct nemo_chain {
   uint32_t len;    /* path length (relationships)                                  */
 } nemo_chain;
 
-/* one missing event of differential provenance (differential-provenance.go:82-146) */
+/* one missing event of differential provenance (differential-provenance.go:82-146),
+ * or one surplus event of the symmetric diff (nemo_fetch_surplus)              */
 typedef struct nemo_missing {
   uint32_t entry;  /* diff entry (index into the failed-run list)                  */
-  uint32_t rule;   /* local index of the rule in run 0's post graph               */
+  uint32_t rule;   /* local index of the rule in run 0's post graph; for a surplus
+                      event: in the entry's own failed run's post graph            */
 } nemo_missing;
 
 /* ---- run sharding --------------------------------------------
@@ -295,6 +297,32 @@ int nemo_diff_masks_view(nemo_ctx *ctx, const uint8_t **masks, uint64_t *n_entri
 /* Missing rules of every entry; goals = all D-children of each rule.        */
 int nemo_fetch_missing(nemo_ctx *ctx, nemo_missing *out, uint64_t cap, uint64_t *n_out);
 
+/* ---- symmetric differential provenance ("bad - good") ----------------------
+ * The half the reference's API names and never built: `symmetric` of
+ * CreateNaiveDiffProv (differential-provenance.go:18; main.go:160 passes
+ * false).  It is the export query (:22-28) and the leaf query (:82-98) with the
+ * two runs' roles exchanged: for entry e with failed run f and gf = f's raw post
+ * graph, Bad = goals of gf whose label is no post-goal label of run 0;
+ * S = Fwd*(Bad) ∩ Bwd*(Bad) over gf; surplus events = the S rules with an
+ * S-goal child that has no S child, at maximal depth + 1 inside S.  Every entry
+ * uses its own failed run against run 0 (no reference mode: :43's in-place
+ * substitution has no counterpart here).  failed_iters may name any loaded
+ * run, run 0 (whose S is empty) and duplicates included.  With n_failed == 0 or
+ * no run of iteration 0 the call yields zero entries, as nemo_diffprov does.
+ * The state is the call's own: results of a previous nemo_diffprov stay
+ * valid, and the reverse.  Single-device contexts only (a node context
+ * returns NEMO_ERR_STATE).                                                   */
+int nemo_diffprov_symmetric(nemo_ctx *ctx, const uint32_t *failed_iters, size_t n_failed);
+/* S masks of every entry (the export of :22-28, roles exchanged), ragged: entry
+ * e's mask is out[off[e] .. off[e+1]), one byte per node of its own failed
+ * post graph.  off has n_entries + 1 elements (may be NULL); out == NULL
+ * queries *n_used (= off[n_entries]).                                        */
+int nemo_fetch_sdiff_masks(nemo_ctx *ctx, uint64_t *off /* n+1 */, uint8_t *out, uint64_t cap, uint64_t *n_used);
+/* Surplus events of every entry (the leaf query of :82-98, roles exchanged),
+ * ordered by (entry, rule); `rule` is local to the entry's failed post graph,
+ * goals = all S-children of each rule.  out == NULL queries *n_out.         */
+int nemo_fetch_surplus(nemo_ctx *ctx, nemo_missing *out, uint64_t cap, uint64_t *n_out);
+
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,
  * async rules of GenerateExtensions (only meaningful when not all achieved).  */
@@ -335,9 +363,11 @@ int nemo_fetch_run_tables(nemo_ctx *ctx, int which, uint32_t *out, uint64_t cap)
 
 /* ---- edge pulls (PullPrePostProv, pre-post-prov.go:288-459; Q24) -----------
  * which = 0: raw graphs, 1: simplified graphs (run 1000+i: kept, not deleted,
- * plus collapsed rules), 2: differential graphs of every diff entry.  The
- * compacted edge lists stay in HBM; `slot` below is the graph index (which
- * 0/1) or the diff entry (which 2).  Collapsed rule k of graph g is reported
+ * plus collapsed rules), 2: differential graphs of every diff entry, 3: the
+ * symmetric diff's graphs (every entry's failed post graph induced on its S,
+ * in that graph's row order; NEMO_ERR_STATE before nemo_diffprov_symmetric).
+ * The compacted edge lists stay in HBM; `slot` below is the graph index (which
+ * 0/1) or the diff entry (which 2/3).  Collapsed rule k of graph g is reported
  * as node index V_g + k.                                                   */
 int nemo_pull_edges(nemo_ctx *ctx, int which);
 uint64_t nemo_pulled_count(nemo_ctx *ctx, uint32_t slot);

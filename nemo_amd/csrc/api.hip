@@ -138,6 +138,18 @@ struct nemo_ctx {
   uint64_t *d_dxw = nullptr;  // [4][nch][V0] Good / LP, B, D, leaf candidates
   bool dx_last = false;              // the last diffprov ran the multi-entry kernels
 
+  // symmetric diff (k_sdiff.hip): all of it the call's own state, so that a symmetric call leaves
+  // the results of a previous nemo_diffprov alone and the reverse; buffers grow only
+  bool sd_done = false;              // a symmetric call completed on the loaded corpus (n_sentries may be 0)
+  uint32_t n_sentries = 0, sd_ecap = 0;
+  uint64_t sd_vcap = 0, sd_bcap = 0;  // nodes the ragged buffers / the global tier's bits hold
+  std::vector<uint32_t> sd_graph;    // entry -> its failed post graph
+  std::vector<uint64_t> sd_off;      // [n + 1] entry -> first node of its slices
+  uint32_t *d_sdgraph = nullptr, *d_sdrows = nullptr, *d_sdn = nullptr;
+  uint64_t *d_sdoff = nullptr;
+  uint8_t *d_sdmask = nullptr, *d_sdbits = nullptr;
+  int32_t *d_sddepth = nullptr;
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -155,7 +167,7 @@ struct nemo_ctx {
   uint32_t h_pslot_cap = 0;
   hipEvent_t ev_pull = nullptr;
   bool pull_synced = true;
-  uint64_t pull_hint[3] = {0, 0, 0};
+  uint64_t pull_hint[4] = {0, 0, 0, 0};
   nemo::PullArgs pull_args{};
 
   // triggers: outputs sized at load from run 0's degrees (exact bounds), one
@@ -563,7 +575,16 @@ static void release_corpus(nemo_ctx *c) {
   c->d_poff = nullptr;
   c->d_pcur = nullptr;
   c->pull_synced = true;
-  c->pull_hint[0] = c->pull_hint[1] = c->pull_hint[2] = 0;
+  c->pull_hint[0] = c->pull_hint[1] = c->pull_hint[2] = c->pull_hint[3] = 0;
+  c->sd_done = false;
+  c->n_sentries = c->sd_ecap = 0;
+  c->sd_vcap = c->sd_bcap = 0;
+  c->sd_graph.clear();
+  c->sd_off.clear();
+  c->d_sdgraph = c->d_sdrows = c->d_sdn = nullptr;
+  c->d_sdoff = nullptr;
+  c->d_sdmask = c->d_sdbits = nullptr;
+  c->d_sddepth = nullptr;
   c->pull_cap = 0;
   c->pull_slot_cap = 0;
   c->d_pck = nullptr;
@@ -2048,6 +2069,147 @@ int nemo_fetch_missing(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
   return NEMO_OK;
 }
 
+// ---- symmetric differential provenance ("bad - good"; DESIGN.md §Symmetric diff) ----
+// Entry e walks its own graph (failed run e's raw post graph) against run 0's
+// post-goal label hash: one launch over all entries, on the context's stream,
+// in call order.  Results stay in HBM until fetched; the state is disjoint
+// from nemo_diffprov's.
+int nemo_diffprov_symmetric(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed) {
+  if (c && c->node)
+    return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric: single-device contexts only (a node context does not fan it out)");
+  if (!c || (!failed_iters && n_failed)) return NEMO_ERR_INVALID;
+  if (!c->loaded) return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric without a loaded corpus (the last load failed?)");
+  if (!c->marked) return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric before nemo_mark_holds");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->n_sentries = 0;
+  c->sd_done = false;
+  c->sd_graph.clear();
+  c->sd_off.assign(1, 0);
+  if (n_failed == 0 || c->run0 < 0) {  // nothing to compare with: zero entries, as nemo_diffprov
+    c->sd_done = true;
+    return NEMO_OK;
+  }
+  if (n_failed > 0xFFFFFFFFull) return fail(c, NEMO_ERR_LIMIT, "too many diff entries");
+  std::vector<uint32_t> graph(n_failed);
+  std::vector<uint64_t> off(n_failed + 1, 0);
+  uint32_t n_lds = 0, n_glob = 0;
+  // algorithmic bytes per entry: rows both ways (8E + 8V), node word + label + Kahn order (12V),
+  // the mask written (V); the three sweeps are counted as traversed edges
+  double bytes = 0, edges = 0;
+  int rc;
+  for (size_t e = 0; e < n_failed; e++) {
+    uint32_t r;
+    if ((rc = run_index(c, failed_iters[e], &r))) return rc;
+    const uint32_t g = 2 * r + 1;
+    const uint64_t V = c->node_off[g + 1] - c->node_off[g], E = c->edge_off[g + 1] - c->edge_off[g];
+    graph[e] = g;
+    off[e + 1] = off[e] + V;
+    if (tier_fits(c->dc.t_diff, (uint32_t)std::min<uint64_t>(V, ~0u), (uint32_t)std::min<uint64_t>(E, ~0u), 0)) n_lds++;
+    else n_glob++;
+    bytes += 8.0 * E + 21.0 * V;
+    edges += 3.0 * E;
+  }
+  const uint64_t total = off[n_failed];
+  const bool grow_v = total > c->sd_vcap || !c->d_sdmask, grow_b = n_glob && (total > c->sd_bcap || !c->d_sdbits);
+  if (n_failed > c->sd_ecap || grow_v || grow_b) {
+    // an earlier symmetric call or its pull may still use the buffers
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_failed > c->sd_ecap) {
+      dfree(c, c->d_sdgraph);
+      dfree(c, c->d_sdoff);
+      c->d_sdgraph = nullptr;
+      c->d_sdoff = nullptr;
+      c->sd_ecap = 0;
+      const uint64_t cap = (n_failed + 63) & ~(uint64_t)63;
+      if ((rc = dalloc(c, &c->d_sdgraph, cap))) return rc;
+      if ((rc = dalloc(c, &c->d_sdoff, cap + 1))) return rc;
+      c->sd_ecap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+    }
+    if (grow_v) {
+      for (void *q : {(void *)c->d_sdmask, (void *)c->d_sddepth, (void *)c->d_sdrows, (void *)c->d_sdbits}) dfree(c, q);
+      c->d_sdmask = c->d_sdbits = nullptr;
+      c->d_sddepth = nullptr;
+      c->d_sdrows = nullptr;
+      c->sd_vcap = c->sd_bcap = 0;
+      if ((rc = dalloc(c, &c->d_sdmask, total))) return rc;
+      if ((rc = dalloc(c, &c->d_sddepth, total))) return rc;
+      // a row per S rule at most, and the rules of all entries are at most their nodes: no overflow
+      if ((rc = dalloc(c, &c->d_sdrows, 2 * total + 2))) return rc;
+      c->sd_vcap = total;
+    }
+    if (grow_b || (n_glob && grow_v)) {  // node bits of the global tier only
+      dfree(c, c->d_sdbits);
+      c->d_sdbits = nullptr;
+      c->sd_bcap = 0;
+      if ((rc = dalloc(c, &c->d_sdbits, c->sd_vcap))) return rc;
+      c->sd_bcap = c->sd_vcap;
+    }
+  }
+  if (!c->d_sdn && (rc = dalloc(c, &c->d_sdn, 1))) return rc;
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->d_sdgraph, graph.data(), n_failed * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_sdoff, off.data(), (n_failed + 1) * 8, hipMemcpyHostToDevice, s));
+  nemo::launch_zero(c->d_sdn, 4, s);
+  nemo::SdiffArgs a{};
+  a.graph = c->d_sdgraph;
+  a.off = c->d_sdoff;
+  a.r0hkey = c->d_r0hkey;
+  a.r0hmask = c->r0hmask;
+  a.bits = c->d_sdbits;
+  a.depth = c->d_sddepth;
+  a.mask = c->d_sdmask;
+  a.rows = c->d_sdrows;
+  a.n_rows = c->d_sdn;
+  if ((rc = timed(c, "k_sdiff", bytes, edges,
+                  [&] { nemo::launch_sdiff(c->dc, a, (uint32_t)n_failed, n_lds, n_glob, s); })))
+    return rc;
+  c->sd_graph = std::move(graph);
+  c->sd_off = std::move(off);
+  c->n_sentries = (uint32_t)n_failed;
+  c->sd_done = true;
+  return NEMO_OK;
+}
+
+int nemo_fetch_sdiff_masks(nemo_ctx *c, uint64_t *off, uint8_t *out, uint64_t cap, uint64_t *n_used) {
+  if (!c) return NEMO_ERR_INVALID;
+  if (!c->sd_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_sdiff_masks before nemo_diffprov_symmetric");
+  const uint64_t total = c->sd_off.back();
+  if (n_used) *n_used = total;
+  if (off) memcpy(off, c->sd_off.data(), c->sd_off.size() * 8);
+  if (!out) return NEMO_OK;
+  if (cap < total) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (total) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_sdmask, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NEMO_OK;
+}
+
+int nemo_fetch_surplus(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n_out) {
+  if (!c) return NEMO_ERR_INVALID;
+  if (!c->sd_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_surplus before nemo_diffprov_symmetric");
+  uint32_t n = 0;
+  if (c->n_sentries) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(&n, c->d_sdn, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (n_out) *n_out = n;
+  if (!out) return NEMO_OK;
+  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (!n) return NEMO_OK;
+  std::vector<uint32_t> rows(2 * (size_t)n);
+  HIPCHK(c, hipMemcpyAsync(rows.data(), c->d_sdrows, 8ull * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  sort_rows<2>(rows.data(), n);  // the device emits in any order: by (entry, rule)
+  for (uint32_t k = 0; k < n; k++) {
+    out[k].entry = rows[2 * k];
+    out[k].rule = rows[2 * k + 1];
+  }
+  return NEMO_OK;
+}
+
 int nemo_triggers(nemo_ctx *c) {
   DISPATCH(node_triggers(c));
   if (!c) return NEMO_ERR_INVALID;
@@ -2345,6 +2507,15 @@ static int pull_launch(nemo_ctx *c) {
   if (a.which == 2) {
     const uint64_t v0 = c->node_off[a.g0 + 1] - c->node_off[a.g0], e0 = c->edge_off[a.g0 + 1] - c->edge_off[a.g0];
     rest = !tier_fits(c->dc.t_pull, (uint32_t)std::min<uint64_t>(v0, ~0u), (uint32_t)std::min<uint64_t>(e0, ~0u), 0);
+  } else if (a.which == 3) {  // every entry has its own graph
+    V = E = 0;
+    rest = 0;
+    for (uint32_t g : c->sd_graph) {
+      const uint64_t v = c->node_off[g + 1] - c->node_off[g], e = c->edge_off[g + 1] - c->edge_off[g];
+      V += (double)v;
+      E += (double)e;
+      rest += !tier_fits(c->dc.t_pull, (uint32_t)std::min<uint64_t>(v, ~0u), (uint32_t)std::min<uint64_t>(e, ~0u), 0);
+    }
   }
   int rc = timed_on(c, s, "k_pull", 4 * E + 13 * V, E, [&] { nemo::launch_pull(c->dc, a, slots, rest, s); });
   if (rc) return rc;
@@ -2403,13 +2574,15 @@ static int pull_sync(nemo_ctx *c) {
 
 int nemo_pull_edges(nemo_ctx *c, int which) {
   DISPATCH(node_pull_edges(c, which));
-  if (!c || which < 0 || which > 2) return NEMO_ERR_INVALID;
+  if (!c || which < 0 || which > 3) return NEMO_ERR_INVALID;
   if (!c->loaded) return fail(c, NEMO_ERR_STATE, "no corpus loaded");
   if (which == 1 && !c->simplified) return fail(c, NEMO_ERR_STATE, "simplified pull before nemo_simplify");
+  if (which == 3 && !c->sd_done)
+    return fail(c, NEMO_ERR_STATE, "symmetric diff pull (which 3) before nemo_diffprov_symmetric");
   HIPCHK(c, hipSetDevice(c->device));
   int rc = ensure_load_checked(c);
   if (rc) return rc;
-  const uint32_t slots = which == 2 ? c->n_entries : c->G;
+  const uint32_t slots = which == 2 ? c->n_entries : which == 3 ? c->n_sentries : c->G;
   // the previous pull's slot table may still be in flight into the pinned tables: wait for it
   // only when they are about to be reallocated (a pull queued behind another on the same
   // stream overwrites the device tables in order; the host reads them in pull_sync after the
@@ -2460,6 +2633,13 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
     a.mask_stride = c->node_off[g0 + 1] - c->node_off[g0];
     a.mask_row = share ? c->d_dsrc + 2 * c->n_entries : nullptr;  // diffprov's representative entries
     cap = (uint64_t)dslots * (c->edge_off[g0 + 1] - c->edge_off[g0]);  // D is an induced subgraph of g0
+  } else if (which == 3) {
+    // slot = entry, graph = the entry's failed post graph, liveness = its S mask (ragged)
+    a.slot_g = c->d_sdgraph;
+    a.mask = c->d_sdmask;
+    a.mask_off = c->d_sdoff;
+    cap = 0;  // S is an induced subgraph of the entry's graph
+    for (uint32_t g : c->sd_graph) cap += c->edge_off[g + 1] - c->edge_off[g];
   } else if (which == 0) {
     cap = c->E;  // every edge
   } else {
@@ -2473,7 +2653,12 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
   a.ccnt = nullptr;
   a.maxck = 0;
   const uint64_t vg0 = c->node_off[g0 + 1] - c->node_off[g0];
-  const uint32_t rows = which == 2 ? (vg0 >= NEMO_CSR_BIG ? dslots : 0u) : c->dc.n_big;
+  uint32_t rows = which == 2 ? (vg0 >= NEMO_CSR_BIG ? dslots : 0u) : c->dc.n_big;
+  if (which == 3) {  // a chunk-table row per entry as soon as one entry's graph is big
+    rows = 0;
+    for (uint32_t g : c->sd_graph)
+      if (c->node_off[g + 1] - c->node_off[g] >= NEMO_CSR_BIG) rows = dslots;
+  }
   if (rows) {
     a.maxck = (uint32_t)(2 * ((c->bigVmax + 4095) / 4096));
     const size_t need = (size_t)rows * a.maxck;

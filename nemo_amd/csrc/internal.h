@@ -123,11 +123,28 @@ struct DxArgs {
   DxImg img[2];              // walk images: Kahn order (Fwd*, depth), reversed (Bwd*)
 };
 
+// One nemo_diffprov_symmetric call (k_sdiff.hip): entry e walks its own graph
+// graph[e] (the failed run's post graph); masks, bits and depths are ragged,
+// entry e's slice starts at off[e] (off[n] = the sum of the entries' nodes).
+struct SdiffArgs {
+  const uint32_t *graph;    // [entries] the entry's graph gf
+  const uint64_t *off;      // [entries + 1] first node of the entry's slices
+  const uint32_t *r0hkey;   // run 0's post-goal labels, open-addressed: key = label + 1 (0 empty)
+  uint32_t r0hmask;         // table size - 1 (power of two)
+  uint8_t *bits;            // [off[n]] node bits of the global tier (null: no such entry)
+  int32_t *depth;           // [off[n]] depths (both tiers; only S nodes touch them)
+  uint8_t *mask;            // [off[n]] S masks (output)
+  uint32_t *rows;           // [2 * off[n]] (entry, rule local to gf)
+  uint32_t *n_rows;         // counter
+};
+
 struct PullArgs {
-  uint32_t which;           // 0 raw, 1 simplified, 2 diff
+  uint32_t which;           // 0 raw, 1 simplified, 2 diff, 3 symmetric diff
   uint32_t g0;              // graph of which == 2
-  const uint8_t *mask;      // which == 2: D masks of the entries
-  uint64_t mask_stride;     // bytes between two entries' masks
+  const uint32_t *slot_g;   // which == 3: slot -> its graph (the entry's failed post graph)
+  const uint8_t *mask;      // which >= 2: D / S masks of the entries
+  uint64_t mask_stride;     // which == 2: bytes between two entries' masks
+  const uint64_t *mask_off; // which == 3: first mask byte of every slot (ragged masks)
   const uint32_t *mask_row; // which == 2: slot -> the entry whose mask it takes (null: the slot's own)
   uint32_t *cnt;            // [slots] edges of the slot
   uint64_t *off;            // [slots] first edge of the slot in src/dst
@@ -166,6 +183,9 @@ void launch_diff(const DevCorpus &c, const DiffArgs &a, uint32_t n_entries, uint
 // entry e's D mask = unique result map[e]'s ([n_entries][V0] from [n_uniq][V0])
 void launch_diff_expand(uint8_t *mask, const uint8_t *umask, const uint32_t *map, uint64_t V0, uint32_t n_entries,
                         hipStream_t s);
+// n_lds / n_glob: entries inside / past k_diff_lds's caps (host counts; an empty tier is not launched)
+void launch_sdiff(const DevCorpus &c, const SdiffArgs &a, uint32_t n_entries, uint32_t n_lds, uint32_t n_glob,
+                  hipStream_t s);
 void launch_dx_prep(const DevCorpus &c, const DxPrep &p, uint32_t *tsum, hipStream_t s);
 void launch_dx(const DevCorpus &c, const DxArgs &a, hipStream_t s);
 uint32_t dx_max_row();       // the longest row of g0 the multi-entry diff takes

@@ -585,6 +585,17 @@ __device__ __forceinline__ bool pull_alive(uint32_t which, const uint8_t *f, con
   if (which == 1) return (f[v] & (NEMO_F_KEPT | NEMO_F_DELETED)) == NEMO_F_KEPT;
   return m[v] != 0;
 }
+// graph and liveness mask of a pull slot: the slot's own graph (raw / simplified), run 0's post
+// graph with entry-major D masks (which 2), or the entry's failed post graph with ragged S masks
+// (which 3, the symmetric diff)
+__device__ __forceinline__ uint32_t pull_graph(const PullArgs &a, uint32_t slot) {
+  return a.which == 2 ? a.g0 : a.which == 3 ? a.slot_g[slot] : slot;
+}
+__device__ __forceinline__ const uint8_t *pull_mask(const PullArgs &a, uint32_t slot) {
+  if (!a.mask) return nullptr;
+  if (a.mask_off) return a.mask + a.mask_off[slot];
+  return a.mask + (size_t)(a.mask_row ? a.mask_row[slot] : slot) * a.mask_stride;
+}
 
 // exclusive scan of cnt[0..n) into off[0..n], one workgroup: every thread
 // sums a contiguous slice (independent loads), one block scan of the slice
@@ -633,7 +644,7 @@ __device__ __forceinline__ void pull_slot(const DevCorpus c, const PullArgs a, c
   __shared__ uint32_t s_lds[(B / 64)];
   __shared__ uint32_t s_cnt;
   __shared__ unsigned long long s_base;
-  const uint32_t g = a.which == 2 ? a.g0 : slot;
+  const uint32_t g = pull_graph(a, slot);
   if (c.err[g]) {
     if (threadIdx.x == 0) {
       a.cnt[slot] = 0;
@@ -644,7 +655,7 @@ __device__ __forceinline__ void pull_slot(const DevCorpus c, const PullArgs a, c
   const GraphView gv = c.view(g);
   if (tier_fits(c.t_pull, gv.V, gv.E, gv.nlev)) return;  // k_pull_lds's graph or diff entry
   if (a.ccnt && gv.V >= NEMO_CSR_BIG) return;             // k_mwp_*'s graph
-  const uint8_t *m = a.mask ? a.mask + (size_t)(a.mask_row ? a.mask_row[slot] : slot) * a.mask_stride : nullptr;
+  const uint8_t *m = pull_mask(a, slot);
   const uint32_t *ch = c.chain + 5 * gv.n0;
   const uint32_t nch = a.which == 1 ? c.nch[g] : 0u;
   if (threadIdx.x == 0) s_cnt = 0;
@@ -736,9 +747,9 @@ struct MwpSlot {
 };
 __device__ __forceinline__ bool mwp_slot(const DevCorpus &c, const PullArgs &a, uint32_t y, MwpSlot &s,
                                          GraphView &gv) {
-  if (a.which == 2) {
+  if (a.which >= 2) {
     s.slot = y;
-    s.g = a.g0;
+    s.g = pull_graph(a, y);
   } else {
     if (y >= c.n_big) return false;
     s.g = s.slot = c.big[y];
@@ -749,7 +760,7 @@ __device__ __forceinline__ bool mwp_slot(const DevCorpus &c, const PullArgs &a, 
   const uint32_t nch = a.which == 1 ? c.nch[s.g] : 0u;
   s.nnc = (gv.V + MWP_CH - 1) / MWP_CH;
   s.nt = s.nnc + (nch + MWP_CH - 1) / MWP_CH;
-  s.m = a.mask ? a.mask + (size_t)(a.mask_row ? a.mask_row[s.slot] : s.slot) * a.mask_stride : nullptr;
+  s.m = pull_mask(a, s.slot);
   return true;
 }
 // edges of node u (raw / simplified / diff row) or of chain k (collapsed edges)
@@ -877,7 +888,7 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_pull_sel(DevCorpus c, uint32_t s
 template <int B>
 __global__ __launch_bounds__(B) void k_pull(DevCorpus c, PullArgs a) {
   // diff pulls: one workgroup per entry (gridDim.x == slots)
-  const bool list = a.which != 2;
+  const bool list = a.which < 2;
   const uint32_t n = list ? c.sel[0] : gridDim.x;
   for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
     pull_slot<B>(c, a, list ? c.sel[1 + k] : k);
@@ -919,7 +930,7 @@ __global__ __launch_bounds__(PULL_BLOCK) void k_pull_lds(DevCorpus c, PullArgs a
   __shared__ uint32_t s_cnt, s_nn;
   __shared__ unsigned long long s_base;
   const uint32_t which = a.which, slot = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-  const uint32_t g = which == 2 ? a.g0 : slot;
+  const uint32_t g = pull_graph(a, slot);
   if (c.err[g]) {  // the empty slot (k_pull, which also writes it, runs only when the host sees graphs past the tier)
     if (tid == 0) {
       a.cnt[slot] = 0;
@@ -933,7 +944,7 @@ __global__ __launch_bounds__(PULL_BLOCK) void k_pull_lds(DevCorpus c, PullArgs a
   PullLds L = pull_carve(dyn, V, gv.E);
   if (which != 0 && V) {
     // diff pulls read the entry's D mask where the others read the flags
-    const uint8_t *fsrc = which == 2 ? a.mask + (size_t)(a.mask_row ? a.mask_row[slot] : slot) * a.mask_stride : gv.flags;
+    const uint8_t *fsrc = which >= 2 ? pull_mask(a, slot) : gv.flags;
     uint32_t f[PULL_K];
 #pragma unroll
     for (int k = 0; k < PULL_K; k++) f[k] = fsrc[min(k * PULL_BLOCK + tid, V - 1u)];  // unconditional: one wait
@@ -1363,7 +1374,7 @@ void launch_pull(const DevCorpus &c, const PullArgs &a, uint32_t slots, uint32_t
   uint32_t grid = slots;
   if (!slots) return;
   if (!global) {
-  } else if (a.which != 2) {
+  } else if (a.which < 2) {
     launch_zero(c.sel, sizeof(uint32_t), s);
     hipLaunchKernelGGL(k_pull_sel, dim3((slots + NEMO_BLOCK - 1) / NEMO_BLOCK), dim3(NEMO_BLOCK), 0, s, c, slots);
     grid = std::min(slots, PULL_GRID);
@@ -1375,7 +1386,7 @@ void launch_pull(const DevCorpus &c, const PullArgs &a, uint32_t slots, uint32_t
       hipLaunchKernelGGL(k_pull<NEMO_BLOCK>, dim3(grid), dim3(NEMO_BLOCK), 0, s, c, a);
   }
   if (!a.ccnt) return;
-  const uint32_t rows = a.which == 2 ? slots : c.n_big;
+  const uint32_t rows = a.which >= 2 ? slots : c.n_big;
   if (!rows) return;
   hipLaunchKernelGGL(k_mwp_count, dim3(a.maxck, rows), dim3(MWP_BLOCK), 0, s, c, a);
   hipLaunchKernelGGL(k_mwp_scan, dim3(rows), dim3(MWP_BLOCK), 0, s, c, a);

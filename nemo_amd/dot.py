@@ -421,3 +421,31 @@ def create_diff_dot(diff_run: int, diff_edges: List[Tuple[ProvNode, ProvNode]],
         if failed.nodes[e.src].get("style") == solid and failed.nodes[e.dst].get("style") == solid:
             e.attrs["style"] = solid
     return diff, failed
+
+
+# ---- symmetric diff: the failed run's own DOT with S marked ---------------------------
+# createDOT / createDiffDot (graphing/diagrams.go) mark nodes and edges with label, style,
+# color, fontcolor, fillcolor and shape only; the S marks use two attributes they never set,
+# so a marked graph keeps every colour and style the reference's report reads.
+SURPLUS_PENWIDTH = '"3"'      # nodes and edges of S
+SURPLUS_PERIPHERIES = '"2"'   # nodes of a surplus event (its rule and the rule's S goals)
+
+
+def create_surplus_dot(failed_edges: List[Tuple[ProvNode, ProvNode]], s_nodes: List[ProvNode],
+                       s_edges: List[Tuple[ProvNode, ProvNode]], surplus_ids: set) -> DotGraph:
+    """The failed run's post provenance as createDOT draws it (diagrams.go:15-130), with the
+    part run 0 lacks marked: `s_nodes` / `s_edges` are S and its induced edges (a Bad goal
+    without an S neighbour is in `s_nodes` only), `surplus_ids` every surplus event's rule ID
+    and goal IDs.  No reference counterpart: `symmetric` (differential-provenance.go:18) was
+    never implemented there."""
+    g = create_dot(failed_edges, "post")
+    for n in s_nodes:
+        if n.id not in g.nodes:  # a node without any edge is not in createDOT's graph
+            g.add_node("dataflow", n.id, _node_attrs(n, "post"))
+        g.nodes[n.id]["penwidth"] = SURPLUS_PENWIDTH
+        if n.id in surplus_ids:
+            g.nodes[n.id]["peripheries"] = SURPLUS_PERIPHERIES
+    for f, t in s_edges:
+        for e in g.src_to_dsts.get((f.id, t.id), []):
+            e.attrs["penwidth"] = SURPLUS_PENWIDTH
+    return g

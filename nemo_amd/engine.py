@@ -94,6 +94,9 @@ def lib():
             "nemo_fetch_missing": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_diff_masks": ([vp, vp, u64], i32),
             "nemo_diff_masks_view": ([vp, vp, vp, vp], i32),
+            "nemo_diffprov_symmetric": ([vp, vp, sz], i32),
+            "nemo_fetch_sdiff_masks": ([vp, vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_surplus": ([vp, vp, u64, P(u64)], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -162,6 +165,7 @@ class Engine:
             raise NemoError(rc, "context creation failed (no HIP device?)")
         self.h = h
         self.corpus: Optional[Corpus] = None
+        self._n_sym = 0  # entries of the last diffprov_symmetric
 
     def devices(self) -> List[int]:
         out = np.zeros(64, np.int32)
@@ -261,6 +265,13 @@ class Engine:
     def diffprov(self, failed: Sequence[int], mode: int = 0) -> None:
         f = np.ascontiguousarray(failed, dtype=np.uint32)
         self._chk(self.L.nemo_diffprov(self.h, _p(f), len(f), mode))
+
+    def diffprov_symmetric(self, failed: Sequence[int]) -> None:
+        """nemo_diffprov_symmetric: for every entry, the part of its failed run's post provenance
+        that run 0 lacks (S masks, surplus events; pull(3) for the induced edges)."""
+        f = np.ascontiguousarray(failed, dtype=np.uint32)
+        self._chk(self.L.nemo_diffprov_symmetric(self.h, _p(f), len(f)))
+        self._n_sym = len(f) if 0 in set(int(x) for x in self.corpus.iteration) else 0
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
         """nemo_goal_labels: [n, label...] of a run's goal labels into device memory."""
@@ -376,6 +387,25 @@ class Engine:
         self._chk(self.L.nemo_fetch_missing(self.h, None, 0, ctypes.byref(n)))
         buf = (CMissing * max(n.value, 1))()
         self._chk(self.L.nemo_fetch_missing(self.h, buf, n.value, ctypes.byref(n)))
+        return np.frombuffer(buf, dtype=np.uint32).reshape(-1, 2)[:n.value].copy()
+
+    def sdiff_masks(self) -> List[np.ndarray]:
+        """S mask of every symmetric-diff entry: one uint8 array per entry, over the nodes of the
+        entry's own failed post graph."""
+        n = ctypes.c_uint64()
+        ne = self._n_sym
+        off = np.zeros(ne + 1, np.uint64)
+        self._chk(self.L.nemo_fetch_sdiff_masks(self.h, off.ctypes.data, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint8)
+        self._chk(self.L.nemo_fetch_sdiff_masks(self.h, None, _p(out), n.value, ctypes.byref(n)))
+        return [out[int(off[e]):int(off[e + 1])].copy() for e in range(ne)]
+
+    def surplus(self) -> np.ndarray:
+        """Surplus events of the symmetric diff as rows (entry, rule local to the entry's failed post graph)."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_surplus(self.h, None, 0, ctypes.byref(n)))
+        buf = (CMissing * max(n.value, 1))()
+        self._chk(self.L.nemo_fetch_surplus(self.h, buf, n.value, ctypes.byref(n)))
         return np.frombuffer(buf, dtype=np.uint32).reshape(-1, 2)[:n.value].copy()
 
     def trigger_rows(self):

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import engine as E
 from .corpus import DIFF_REFERENCE, F_HOLDS, NODE_RULE, TABLE_MASK, Corpus
-from .dot import DotGraph, ProvNode, create_diff_dot, create_dot, read_dot
+from .dot import DotGraph, ProvNode, create_diff_dot, create_dot, create_surplus_dot, read_dot
 
 
 # ---- faultinjectors/data-types.go:43-78 -------------------------------------------
@@ -179,6 +179,7 @@ class Neo4J:
         self._chains: Dict[int, List[Tuple[int, int]]] = {}
         self._protos: Optional[dict] = None
         self.diff_mode = DIFF_REFERENCE
+        self.SurplusEvents: List[List[Missing]] = []  # CreateNaiveDiffProv(True, ...): per failed run
 
     # ---- helpers.go -------------------------------------------------------------
     def InitGraphDB(self, boltURI: str, runs: Corpus, device: int = 0) -> None:
@@ -317,7 +318,10 @@ class Neo4J:
     # ---- differential-provenance.go ---------------------------------------------
     def CreateNaiveDiffProv(self, symmetric: bool, failedRuns: Sequence[int], successPostProv: DotGraph):
         """differential-provenance.go:18-243 -> (diffDots, failedDots, missingEvents).
-        `symmetric` is unused, as in the reference."""
+        `symmetric` False: as the reference, which never reads the flag.  True: the half the flag
+        was named for is computed too (nemo_diffprov_symmetric): failedDots[e] is then the failed
+        run's own post provenance with the part run 0 lacks marked (dot.create_surplus_dot) and
+        self.SurplusEvents[e] its surplus events; diffDots and missingEvents are unchanged."""
         c = self.Runs
         r0 = c.run_index(0)
         g0 = 2 * r0 + 1
@@ -351,7 +355,38 @@ class Neo4J:
             d, fd = create_diff_dot(2000 + int(f), diff_edges[e], failed_edges, 0, successPostProv, ids)
             diffs.append(d)
             faileds.append(fd)
+        if symmetric:
+            faileds = self._surplus(failedRuns)
         return diffs, faileds, missing
+
+    def _surplus(self, failedRuns: Sequence[int]) -> List[DotGraph]:
+        """The symmetric half: S masks, surplus events (kept in self.SurplusEvents) and the
+        marked DOT of every failed run."""
+        c = self.Runs
+        self.eng.diffprov_symmetric(failedRuns)
+        masks = self.eng.sdiff_masks()
+        rows = self.eng.surplus()
+        self.eng.pull(3)
+        self.SurplusEvents = [[] for _ in failedRuns]
+        dots = []
+        for e, f in enumerate(failedRuns):
+            gf = self._g(int(f), "post")
+            s_edges = self._edges(e, gf) if len(masks) else []
+            mask = masks[e] if len(masks) else np.zeros(c.graph_size(gf), np.uint8)
+            e0, e1 = int(c.edge_off[gf]), int(c.edge_off[gf + 1])
+            src, dst = c.edge_src[e0:e1], c.edge_dst[e0:e1]
+            ids = set()
+            for rule in sorted(int(r) for en, r in rows.tolist() if en == e):
+                m = Missing(self._rule(self._node(gf, rule)))
+                for ch in sorted(int(x) for x in dst[src == rule]):
+                    if mask[ch]:
+                        m.Goals.append(self._goal(self._node(gf, ch)))
+                self.SurplusEvents[e].append(m)
+                ids.add(m.Rule.ID)
+                ids.update(gl.ID for gl in m.Goals)
+            s_nodes = [self._node(gf, int(i)) for i in np.nonzero(mask)[0]]
+            dots.append(create_surplus_dot(self._edges(None, gf), s_nodes, s_edges, ids))
+        return dots
 
     # ---- corrections.go / extensions.go -----------------------------------------
     def _trigger_rows(self):
