@@ -1099,11 +1099,11 @@ int nemo_load_corpus(nemo_ctx *c, const nemo_corpus *in) {
   if ((rc = dalloc(c, &(p), (n)))) return rc
   A(no, G + 1);
   A(eo, G + 1);
-  A(word, V);
+  A(word, V + NEMO_IN_PAD);  // (k_build's clamped 16-byte loads: internal.h)
   A(label, V);
   if (c->has_rank) A(rank, V);
-  A(es, E);
-  A(ed, E);
+  A(es, E + NEMO_IN_PAD);
+  A(ed, E + NEMO_IN_PAD);
   A(d.fp, V + G);
   A(d.rp, V + G);
   A(d.fc, E);

@@ -164,6 +164,9 @@ struct TrigArgs {
 };
 
 __host__ __device__ uint32_t build_tier_bytes(uint32_t v, uint32_t e);
+// entries the device copies of the edge arrays and the node words end with: k_build's 16-byte input
+// loads at an index clamped to a graph's end read up to this many entries past the last graph
+#define NEMO_IN_PAD 4
 void launch_build(const DevCorpus &c, hipStream_t s);
 void launch_load(const DevCorpus &c, hipStream_t s);
 void launch_topo(const DevCorpus &c, hipStream_t s, bool list = true);

@@ -59,6 +59,9 @@ __device__ void sort_row(uint32_t *r, uint32_t n) {
 #ifndef BLD_KB
 #define BLD_KB 4    // Kahn: children of a node processed per round
 #endif
+#ifndef BLD_NW
+#define BLD_NW 2    // input: 16-byte node-word loads per thread in flight at a time (4: 38 VGPR spills, 6: 62)
+#endif
 
 
 // 5-comparator sorting network for 4 keys
@@ -211,34 +214,37 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(BLD_OCC(B))))
   uint16_t *q16 = (uint16_t *)p;  // Kahn order
   const uint32_t *es = c.esrc + e0, *ed = c.edst + e0, *word = c.word + n0;
   STAMP(10);
-  // every load of the graph's input issued back to back: edge e = tid + q*BLOCK
-  // as (src << 16 | dst), and the rule bits of the node words
-  // (four consecutive edges per thread and 16-byte load; ~0u marks an empty
-  // slot: a valid pair has src < 16384)
+  // every load of the graph's input issued back to back, before the first use
+  // of any: four consecutive edges per thread and 16-byte load (edge e = 4 *
+  // (g4 * B + tid) + b), and the first BLD_NW * 4 * B node words.  The loads
+  // are unconditional at an index clamped to the graph's end: a load in a
+  // branch (a scalar tail beside the 16-byte one) made the compiler wait for
+  // each group of loads before it issued the next, eight round trips to HBM
+  // for the edges and one per load for the words.  A load at the clamped index
+  // reads up to four entries past the graph: the next graph's, or NEMO_IN_PAD
+  // entries the corpus arrays end with (api.hip); the entries past E / V are
+  // masked below.
+  uint4 xs[EPT / 4], ys[EPT / 4], nw[BLD_NW];
+#pragma unroll
+  for (int g4 = 0; g4 < EPT / 4; g4++) {
+    const uint32_t e = min(4u * (g4 * B + tid), E);
+    __builtin_memcpy(&xs[g4], es + e, 16);
+    __builtin_memcpy(&ys[g4], ed + e, 16);
+  }
+#pragma unroll
+  for (int g4 = 0; g4 < BLD_NW; g4++) __builtin_memcpy(&nw[g4], word + min(4u * (g4 * B + tid), V), 16);
+  // edges as (src << 16 | dst); ~0u marks an empty slot: a valid pair has src < 16384
   uint32_t sd[EPT];
   bool bad = false;
 #pragma unroll
   for (int g4 = 0; g4 < EPT / 4; g4++) {
     const uint32_t e0 = 4 * (g4 * B + tid);
-    uint32_t xs[4], ys[4];
-    if (e0 + 3 < E) {
-      uint4 a4, b4;
-      __builtin_memcpy(&a4, es + e0, 16);
-      __builtin_memcpy(&b4, ed + e0, 16);
-      xs[0] = a4.x, xs[1] = a4.y, xs[2] = a4.z, xs[3] = a4.w;
-      ys[0] = b4.x, ys[1] = b4.y, ys[2] = b4.z, ys[3] = b4.w;
-    } else {
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        xs[b] = e0 + b < E ? es[e0 + b] : 0u;
-        ys[b] = e0 + b < E ? ed[e0 + b] : 0u;
-      }
-    }
+    const uint32_t x[4] = {xs[g4].x, xs[g4].y, xs[g4].z, xs[g4].w}, y[4] = {ys[g4].x, ys[g4].y, ys[g4].z, ys[g4].w};
 #pragma unroll
     for (int b = 0; b < 4; b++) {
       const bool in = e0 + b < E;
-      bad |= in && (xs[b] >= V || ys[b] >= V);
-      sd[4 * g4 + b] = in ? (xs[b] << 16) | (ys[b] & 0xFFFFu) : ~0u;
+      bad |= in && (x[b] >= V || y[b] >= V);
+      sd[4 * g4 + b] = in ? (x[b] << 16) | (y[b] & 0xFFFFu) : ~0u;
     }
   }
   for (uint32_t w = tid; w < (V + 31) / 32; w += B) s_rule[w] = 0;
@@ -252,26 +258,22 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(BLD_OCC(B))))
   __syncthreads();
   // (four consecutive node words per thread and 16-byte load: eight lanes'
   // nibbles make one bitmap word)
-  for (uint32_t base = 0; base < V; base += 8 * B) {
-    uint32_t nib[2];
+  for (uint32_t base = 0; base < V; base += 4 * BLD_NW * B) {
+    uint32_t nib[BLD_NW];
+    if (base) {  // (a graph past the words loaded above: its next BLD_NW * 4 * B, again all in flight together)
 #pragma unroll
-    for (int g4 = 0; g4 < 2; g4++) {
+      for (int g4 = 0; g4 < BLD_NW; g4++) __builtin_memcpy(&nw[g4], word + min(base + 4u * (g4 * B + tid), V), 16);
+    }
+#pragma unroll
+    for (int g4 = 0; g4 < BLD_NW; g4++) {
       const uint32_t v0 = base + 4 * (g4 * B + tid);
-      uint32_t w[4];
-      if (v0 + 3 < V) {
-        uint4 w4;
-        __builtin_memcpy(&w4, word + v0, 16);
-        w[0] = w4.x, w[1] = w4.y, w[2] = w4.z, w[3] = w4.w;
-      } else {
-#pragma unroll
-        for (int b = 0; b < 4; b++) w[b] = v0 + b < V ? word[v0 + b] : 0u;
-      }
+      const uint32_t w[4] = {nw[g4].x, nw[g4].y, nw[g4].z, nw[g4].w};
       nib[g4] = 0;
 #pragma unroll
       for (int b = 0; b < 4; b++) nib[g4] |= (v0 + b < V && is_rule(w[b]) ? 1u : 0u) << b;
     }
 #pragma unroll
-    for (int g4 = 0; g4 < 2; g4++) {
+    for (int g4 = 0; g4 < BLD_NW; g4++) {
       const uint32_t v0 = base + 4 * (g4 * B + tid);
       uint32_t x = nib[g4] << (4 * (tid & 7));
       x |= (uint32_t)__shfl_xor((int)x, 1);
