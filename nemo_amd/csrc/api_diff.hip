@@ -1,0 +1,505 @@
+// api_diff.hip — differential provenance: nemo_diffprov*, the symmetric diff and their fetches.
+#include "ctx.h"
+
+extern "C" {
+
+// d_labels != NULL: label mode, every entry's failGoals is the device label
+// set [n, label...] (n <= labels_cap), e.g. broadcast from the shard that owns
+// failedRuns[0]; mode is then ignored.
+static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed, int mode,
+                         const uint32_t *d_labels, uint64_t labels_cap) {
+  if (!c || (!failed_iters && n_failed)) return NEMO_ERR_INVALID;
+  if (mode != NEMO_DIFF_REFERENCE && mode != NEMO_DIFF_PER_RUN) return fail(c, NEMO_ERR_INVALID, "unknown diff mode %d", mode);
+  if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "nemo_diffprov without a loaded corpus (the last load failed?)");
+  if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "nemo_diffprov before nemo_mark_holds");
+  // (the diff kernels read no holds flags: a deferred mark stays fused with the simplification)
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cs.n_entries = 0;
+  if (n_failed == 0 || c->cs.run0 < 0) return NEMO_OK;  // MATCH on run 0 finds nothing
+  if (int re = ensure_event(c, &c->ev_up_dsrc)) return re;
+  HIPCHK(c, hipEventSynchronize(c->ev_up_dsrc));  // the previous upload has landed (at once if there was none)
+  if (int rg = c->h_dsrc.grow(c, 3 * n_failed)) return rg;
+  // D_f depends on run 0 and on the label source alone (differential-provenance.go:22-43):
+  // entries with the same source share one computation.  In the reference mode every
+  // entry's source is failedRuns[0] (the in-place ###RUN### substitution of :43), so
+  // the whole call is one computation; in the per-run mode each distinct failed run is.
+  uint32_t *src = c->h_dsrc.p, *emap = c->h_dsrc.p + n_failed, *urep = c->h_dsrc.p + 2 * n_failed;
+  c->cs.dmap.assign(n_failed, 0);
+  std::unordered_map<uint32_t, uint32_t> uniq;
+  uint32_t nu = 0;
+  double src_bytes = 0;  // the label sources' HBM reads (word + label per node, or the label set)
+  for (size_t e = 0; e < n_failed; e++) {
+    uint32_t r;
+    const uint32_t it = mode == NEMO_DIFF_PER_RUN && !d_labels ? failed_iters[e] : failed_iters[0];
+    int rc = run_index(c, d_labels ? failed_iters[e] : it, &r);
+    if (rc) return rc;
+    const uint32_t key = d_labels ? 0u : 2 * r + 1;  // label mode: one set for every entry
+    auto ins = uniq.emplace(key, nu);
+    if (ins.second) {
+      urep[nu] = (uint32_t)e;  // the first entry of each source stands for it (nemo_pull_edges(2))
+      src[nu++] = 2 * r + 1;
+      src_bytes += d_labels ? 0.0 : 8.0 * (double)(c->cs.node_off[2 * r + 2] - c->cs.node_off[2 * r + 1]);
+    }
+    c->cs.dmap[e] = emap[e] = ins.first->second;
+  }
+  if (d_labels) src_bytes = 4.0 * (double)labels_cap;  // read once, then L2-resident
+  const bool expand = nu < n_failed;
+  const uint32_t g0 = 2 * c->cs.run0 + 1;
+  const uint64_t V0 = c->cs.node_off[g0 + 1] - c->cs.node_off[g0];
+  const uint64_t E0 = c->cs.edge_off[g0 + 1] - c->cs.edge_off[g0];
+  const bool dx = c->cs.dx_ok && !c->opt.diff_legacy && (c->opt.diff_window != 2 || c->cs.g0_maxdeg <= nemo::dx_max_row_tiny());
+  int rc;
+  // capacities in whole 64-entry chunks: the per-entry buffers of corpora (batches) with a few more
+  // or fewer failed runs are the same size, so the allocation cache hands the same blocks back (a
+  // block no load takes is freed at the next load, and hipFree waits for the whole device)
+  const uint64_t nf_cap = (n_failed + 63) & ~(uint64_t)63;
+  if (n_failed > c->cs.diff_cap) {
+    for (void *q : {(void *)c->cs.d_dsrc, (void *)c->cs.d_dmask, (void *)c->cs.d_miss, (void *)c->cs.d_dbits, (void *)c->cs.d_dumask,
+                    (void *)c->cs.d_ddepth, (void *)c->cs.d_dtopo})
+      dfree(c, q);
+    c->cs.d_dbits = c->cs.d_dumask = nullptr;
+    c->cs.d_ddepth = nullptr;
+    c->cs.d_dtopo = nullptr;
+    c->cs.legacy_cap = 0;
+    if ((rc = dalloc(c, &c->cs.d_dsrc, 3 * nf_cap))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_dmask, nf_cap * V0))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_miss, 2 * nf_cap * (V0 + 1)))) return rc;
+    c->cs.diff_cap = (uint32_t)nf_cap;
+  }
+  if (!dx && n_failed > c->cs.legacy_cap) {  // the one-workgroup-per-entry kernels' scratch
+    for (void *q : {(void *)c->cs.d_dbits, (void *)c->cs.d_dumask, (void *)c->cs.d_ddepth, (void *)c->cs.d_dtopo}) dfree(c, q);
+    c->cs.d_dbits = c->cs.d_dumask = nullptr;
+    c->cs.d_ddepth = nullptr;
+    c->cs.d_dtopo = nullptr;
+    if ((rc = dalloc(c, &c->cs.d_dbits, nf_cap * V0))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_dumask, nf_cap * V0))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_ddepth, nf_cap * V0))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_dtopo, 4 * V0 + 2 * E0 + 2 + c->cs.n_r0lab))) return rc;
+    c->cs.legacy_cap = (uint32_t)nf_cap;
+  }
+  const uint32_t nch = (nu + 63) / 64, w32 = (uint32_t)((V0 + 31) / 32), nu_cap = 64 * nch;
+  if (dx && (nu > c->cs.dx_nu_cap || nch > c->cs.dx_nch_cap)) {
+    for (void *q : {(void *)c->cs.d_dxpb, (void *)c->cs.d_dxsval, (void *)c->cs.d_dxlpl, (void *)c->cs.d_dxw, (void *)c->cs.d_dxfb})
+      dfree(c, q);
+    c->cs.d_dxpb = c->cs.d_dxsval = c->cs.d_dxlpl = c->cs.d_dxfb = nullptr;
+    c->cs.d_dxw = nullptr;
+    c->cs.dx_nu_cap = c->cs.dx_nch_cap = 0;
+    if ((rc = dalloc(c, &c->cs.d_dxpb, (size_t)nu_cap * w32))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_dxsval, (size_t)nu_cap * V0))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_dxlpl, (size_t)nu_cap + nch))) return rc;  // maxima, then the chunks' walk flags
+    if ((rc = dalloc(c, &c->cs.d_dxw, 4 * (size_t)nch * V0))) return rc;
+    if ((rc = dalloc(c, &c->cs.d_dxfb, 8 * (size_t)nch * V0))) return rc;  // 32 bytes per position and chunk
+    c->cs.dx_nu_cap = nu_cap;
+    c->cs.dx_nch_cap = nch;
+  }
+  if (!c->cs.d_nmiss && (rc = dalloc(c, &c->cs.d_nmiss, 1))) return rc;
+  c->cs.d_dmap = c->cs.d_dsrc + n_failed;
+  c->cs.n_uniq = nu;
+  // the diff kernels go on `aux` once `stream` has reached this point (the load /
+  // rebuild of the graphs they read is queued there)
+  hipStream_t s = c->stream;
+  if (c->opt.diff_on_aux) {
+    if (!c->aux) HIPCHK(c, hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
+    if ((rc = ensure_event(c, &c->ev_fork))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
+    s = c->aux;
+  }
+  nemo::launch_to_host(c->cs.d_dsrc, src, 3 * n_failed * 4, s);  // pinned -> device by a copy kernel (no blit queue)
+  HIPCHK(c, hipEventRecord(c->ev_up_dsrc, s));
+  nemo::launch_zero(c->cs.d_nmiss, 4, s);
+  // HBM lower bound: run 0's post graph once (rows both ways, node word, Kahn
+  // order: 8E0 + 16V0 -- every entry re-reads it from L2), each distinct label
+  // source and each entry's D mask (V0); the three reachability sweeps per
+  // computed entry are counted as traversed edges, not as HBM bytes
+  const double bytes = 8.0 * E0 + 16.0 * V0 + src_bytes + (double)n_failed * V0;
+  c->cs.dx_last = dx;
+  if (dx) {
+    nemo::DxArgs a{};
+    a.p = c->cs.dxp;
+    a.nu = nu;
+    a.nch = nch;
+    a.src = c->cs.d_dsrc;
+    a.ref_labels = d_labels;
+    a.r0lab = c->cs.d_r0lab;
+    a.r0hkey = c->cs.d_r0hkey;
+    a.r0hval = c->cs.d_r0hval;
+    a.r0hmask = c->cs.r0hmask;
+    a.r0dense = c->cs.dxp.r0dense;
+    a.nlab = c->cs.nlab;
+    a.pb = c->cs.d_dxpb;
+    a.w32 = w32;
+    uint64_t maxsrc = d_labels ? labels_cap : 0;
+    for (uint32_t u = 0; u < nu && !d_labels; u++)
+      maxsrc = std::max<uint64_t>(maxsrc, c->cs.node_off[src[u] + 1] - c->cs.node_off[src[u]]);
+    a.lab_per = 8192;  // one workgroup per source up to 8192 nodes: its bitmap stored whole, no atomics
+    a.lab_split = (uint32_t)std::max<uint64_t>(1, (maxsrc + a.lab_per - 1) / a.lab_per);
+    const size_t plane = (size_t)nch * V0;
+    a.gw = c->cs.d_dxw;
+    a.bw = a.gw + plane;
+    a.dw = a.bw + plane;
+    a.lw = a.dw + plane;
+    a.fb = reinterpret_cast<uint8_t *>(c->cs.d_dxfb);
+    a.sval = c->cs.d_dxsval;
+    a.maxlen = c->cs.d_dxlpl;
+    a.wflag = c->cs.d_dxlpl + c->cs.dx_nu_cap;
+    a.mask = c->cs.d_dmask;
+    a.map = c->cs.d_dmap;
+    a.n_entries = (uint32_t)n_failed;
+    a.missing = c->cs.d_miss;
+    a.n_missing = c->cs.d_nmiss;
+    a.window = c->opt.diff_window;
+    a.legacy_lp = c->opt.diff_unfused;
+    a.urep = c->cs.d_dsrc + 2 * n_failed;
+    a.own_mask = nu == n_failed ? 1u : 0u;
+    if (c->cs.dx_img_key < 0) {
+      // g0 in Kahn order (read the Kahn order, both CSRs and the node words;
+      // write positions, rows both ways, level bounds), once per load / rebuild
+      c->cs.dxp.err0 = c->cs.dc.err + c->cs.dxp.g0;
+      if ((rc = timed_on(c, s, "k_dxprep", 16.0 * E0 + 44.0 * V0, 0,
+                         [&] { nemo::launch_dx_prep(c->cs.dc, c->cs.dxp, c->cs.dx_its.tsum, s); })))
+        return rc;
+    }
+    if (c->cs.dx_img_key != (int)c->opt.diff_window) {
+      // the walk images (read rows and Kahn levels, write records, steps and
+      // misses), once per load / rebuild and window configuration (test knob)
+      nemo::dx_img_configs(c->cs.dxp.V0, c->cs.dxp.E0, c->opt.diff_window, c->cs.dx_img);
+      if ((rc = timed_on(c, s, "k_dximg", 2 * (16.0 * E0 + 32.0 * V0), 0,
+                         [&] { nemo::launch_dx_img(c->cs.dxp, c->cs.dx_img, c->cs.dx_its, s); })))
+        return rc;
+      c->cs.dx_img_key = (int)c->opt.diff_window;
+    }
+    for (int k = 0; k < 2; k++) a.img[k] = c->cs.dx_img[k];
+    rc = timed_on(c, s, "k_diff", bytes, (double)nu * 3 * E0, [&] { nemo::launch_dx(c->cs.dc, a, s); });
+  } else {
+    nemo::DiffArgs a;
+    a.g0 = g0;
+    a.src = c->cs.d_dsrc;
+    a.ref_labels = d_labels;
+    a.r0lab = c->cs.d_r0lab;
+    a.r0idx = c->cs.d_r0idx;
+    a.n_r0lab = c->cs.n_r0lab;
+    a.r0hkey = c->cs.d_r0hkey;
+    a.r0hval = c->cs.d_r0hval;
+    a.r0hmask = c->cs.r0hmask;
+    a.bits = c->cs.d_dbits;
+    a.depth = c->cs.d_ddepth;
+    a.tpos = c->cs.d_dtopo;
+    a.tinfo = a.tpos + V0;
+    a.trp = a.tinfo + V0;
+    a.tfp = a.trp + V0 + 1;
+    a.trc = a.tfp + V0 + 1;
+    a.tfc = a.trc + E0;
+    a.r0pos = a.tfc + E0;
+    a.mask = expand ? c->cs.d_dumask : c->cs.d_dmask;
+    a.missing = c->cs.d_miss;
+    a.n_missing = c->cs.d_nmiss;
+    rc = timed_on(c, s, "k_diff", bytes, (double)nu * 3 * E0,
+                  [&] {
+                    // the Kahn-order relayout only when g0 may fall outside the LDS tier
+                    const bool lds = c->cs.dc.t_diff.bytes && V0 <= c->cs.dc.t_diff.v && E0 <= c->cs.dc.t_diff.e;
+                    nemo::launch_diff(c->cs.dc, a, nu, lds ? 0u : (uint32_t)V0, s);
+                    if (expand) nemo::launch_diff_expand(c->cs.d_dmask, c->cs.d_dumask, c->cs.d_dmap, V0, (uint32_t)n_failed, s);
+                  });
+  }
+  if (rc) return rc;
+  // D masks and the missing-event count -> pinned host
+  if ((rc = ensure_event(c, &c->ev_diff))) return rc;
+  if ((rc = c->h_mask.grow(c, n_failed * V0))) return rc;
+  if ((rc = c->h_nmiss.grow(c, (uint64_t)1))) return rc;
+  // the missing rows too, at the last call's count: nemo_fetch_missing then needs no round
+  // trip of its own unless this call found more (d_miss holds n_failed (V0 + 1) rows)
+  c->cs.mrows_staged = std::min<uint64_t>(c->mrows_hint, (uint64_t)n_failed * (V0 + 1));
+  if ((rc = c->h_mrows.grow(c, 2 * c->cs.mrows_staged + 2))) return rc;
+  nemo::HostCopies hc;
+  hc.add(c->h_mask.p, c->cs.d_dmask, n_failed * V0);
+  hc.add(c->h_nmiss.p, c->cs.d_nmiss, 4);
+  hc.add(c->h_mrows.p, c->cs.d_miss, 8 * c->cs.mrows_staged);
+  nemo::launch_to_host_multi(hc, s);
+  HIPCHK(c, hipEventRecord(c->ev_diff, s));
+  c->cs.aux_pending = true;
+  c->cs.n_entries = (uint32_t)n_failed;
+  return NEMO_OK;
+}
+
+int nemo_diffprov(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed, int mode) {
+  DISPATCH(node_diffprov(c, failed_iters, n_failed, mode));
+  return diffprov_impl(c, failed_iters, n_failed, mode, nullptr, 0);
+}
+
+int nemo_diffprov_labels(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed, const uint32_t *d_labels,
+                         uint64_t labels_cap) {
+  DISPATCH(node_diffprov_labels(c, failed_iters, n_failed, d_labels, labels_cap));
+  if (!d_labels) return c ? fail(c, NEMO_ERR_INVALID, "no label set") : NEMO_ERR_INVALID;
+  return diffprov_impl(c, failed_iters, n_failed, NEMO_DIFF_REFERENCE, d_labels, labels_cap);
+}
+
+int nemo_diffprov_host_labels(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed, const uint32_t *labels,
+                              uint64_t n_labels) {
+  DISPATCH(node_diffprov_host_labels(c, failed_iters, n_failed, labels, n_labels));
+  if (!c || (!labels && n_labels)) return NEMO_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = join_aux(c))) return rc;  // the previous diff may still read d_hlab
+  if (n_labels + 1 > c->cs.hlab_cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    dfree(c, c->cs.d_hlab);
+    c->cs.d_hlab = nullptr;
+    c->cs.hlab_cap = 0;
+    if ((rc = dalloc(c, &c->cs.d_hlab, n_labels + 1))) return rc;
+    c->cs.hlab_cap = n_labels + 1;
+  }
+  if ((rc = ensure_event(c, &c->ev_up_hlab))) return rc;
+  HIPCHK(c, hipEventSynchronize(c->ev_up_hlab));  // the previous upload has landed (at once if there was none)
+  if ((rc = c->h_hlab.grow(c, n_labels + 1))) return rc;
+  c->h_hlab.p[0] = (uint32_t)n_labels;
+  if (n_labels) memcpy(c->h_hlab.p + 1, labels, n_labels * 4);
+  nemo::launch_to_host(c->cs.d_hlab, c->h_hlab.p, (n_labels + 1) * 4, c->stream);  // pinned -> device by a copy kernel
+  HIPCHK(c, hipEventRecord(c->ev_up_hlab, c->stream));
+  return diffprov_impl(c, failed_iters, n_failed, NEMO_DIFF_REFERENCE, c->cs.d_hlab, n_labels + 1);
+}
+
+int nemo_goal_labels(nemo_ctx *c, uint32_t iteration, int cond, uint32_t *d_out, uint64_t cap) {
+  DISPATCH(node_goal_labels(c, iteration, cond, d_out, cap));
+  if (!c || !d_out || (cond != 0 && cond != 1)) return NEMO_ERR_INVALID;
+  if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "no corpus loaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rl = ensure_load_checked(c)) return rl;
+  uint32_t r;
+  int rc = run_index(c, iteration, &r);
+  if (rc) return rc;
+  const uint32_t g = 2 * r + (uint32_t)cond;
+  const uint64_t V = c->cs.node_off[g + 1] - c->cs.node_off[g];
+  if (cap < V + 1) return fail(c, NEMO_ERR_INVALID, "label capacity %llu < %llu", (unsigned long long)cap,
+                               (unsigned long long)(V + 1));
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = join_aux(c))) return rc;  // d_out may be the label set a previous diff still reads
+  return timed(c, "k_goal_labels", 8.0 * (double)V, 0, [&] { nemo::launch_goal_labels(c->cs.dc, g, d_out, c->stream); });
+}
+
+int nemo_fetch_diff_mask(nemo_ctx *c, uint32_t entry, uint8_t *out, uint64_t cap) {
+  DISPATCH(node_fetch_diff_mask(c, entry, out, cap));
+  if (!c || !out) return NEMO_ERR_INVALID;
+  if (entry >= c->cs.n_entries) return fail(c, NEMO_ERR_INVALID, "diff entry %u out of range", entry);
+  const uint32_t g0 = 2 * c->cs.run0 + 1;
+  const uint64_t V0 = c->cs.node_off[g0 + 1] - c->cs.node_off[g0];
+  if (cap < V0) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->ev_diff));
+  memcpy(out, c->h_mask.p + (size_t)entry * V0, V0);
+  return NEMO_OK;
+}
+
+int nemo_fetch_diff_masks(nemo_ctx *c, uint8_t *out, uint64_t cap) {
+  DISPATCH(node_fetch_diff_masks(c, out, cap));
+  if (!c || !out) return NEMO_ERR_INVALID;
+  if (!c->cs.n_entries) return NEMO_OK;
+  const uint32_t g0 = 2 * c->cs.run0 + 1;
+  const uint64_t n = (uint64_t)c->cs.n_entries * (c->cs.node_off[g0 + 1] - c->cs.node_off[g0]);
+  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->ev_diff));
+  memcpy(out, c->h_mask.p, n);
+  return NEMO_OK;
+}
+
+int nemo_diff_masks_view(nemo_ctx *c, const uint8_t **masks, uint64_t *n_entries, uint64_t *v0) {
+  DISPATCH(node_diff_masks_view(c, masks, n_entries, v0));
+  if (!c || !masks) return NEMO_ERR_INVALID;
+  *masks = nullptr;
+  if (n_entries) *n_entries = c->cs.n_entries;
+  const uint32_t g0 = c->cs.run0 >= 0 ? 2 * c->cs.run0 + 1 : 0;
+  if (v0) *v0 = c->cs.run0 >= 0 ? c->cs.node_off[g0 + 1] - c->cs.node_off[g0] : 0;
+  if (!c->cs.n_entries) return NEMO_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->ev_diff));
+  *masks = c->h_mask.p;
+  return NEMO_OK;
+}
+
+int nemo_fetch_missing(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n_out) {
+  DISPATCH(node_fetch_missing(c, out, cap, n_out));
+  if (!c) return NEMO_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  uint32_t nu_rows = 0;
+  if (c->cs.n_entries) {
+    HIPCHK(c, hipEventSynchronize(c->ev_diff));
+    nu_rows = *c->h_nmiss.p;
+    // the fused walks' bounded hand-off wait (k_dx.hip dx_publish) gave up: the rows are void
+    if (c->cs.dx_last && (nu_rows & DX_ERR_HANDOFF))
+      return fail(c, NEMO_ERR_INVALID, "diff walks: a longest-path workgroup timed out waiting for its Bwd* hand-off");
+    nu_rows &= DX_ROWS;
+  }
+  // rows of the distinct computations (unique index, rule), then one copy per entry
+  int rc;
+  if ((rc = ensure_event(c, &c->ev_misc))) return rc;
+  if (nu_rows > c->cs.mrows_staged) {  // more rows than diffprov copied with the masks
+    if ((rc = c->h_mrows.grow(c, 2 * (uint64_t)nu_rows + 2))) return rc;
+    if ((rc = join_aux(c))) return rc;
+    nemo::launch_to_host(c->h_mrows.p, c->cs.d_miss, 8ull * nu_rows, c->stream);
+    HIPCHK(c, hipEventRecord(c->ev_misc, c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev_misc));
+    c->cs.mrows_staged = nu_rows;
+  }
+  c->mrows_hint = std::max<uint64_t>(256, nu_rows);
+  const uint32_t *rows = c->h_mrows.p;
+  std::vector<std::vector<uint32_t>> per(c->cs.n_uniq);
+  for (uint32_t i = 0; i < nu_rows; i++) per[rows[2 * i]].push_back(rows[2 * i + 1]);
+  uint64_t n = 0;
+  for (auto &v : per) std::sort(v.begin(), v.end());
+  for (uint32_t e = 0; e < c->cs.n_entries; e++) n += per[c->cs.dmap[e]].size();
+  if (n_out) *n_out = n;
+  if (!out) return NEMO_OK;
+  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  uint64_t k = 0;
+  for (uint32_t e = 0; e < c->cs.n_entries; e++)
+    for (uint32_t r : per[c->cs.dmap[e]]) {
+      out[k].entry = e;
+      out[k].rule = r;
+      k++;
+    }
+  return NEMO_OK;
+}
+
+// ---- symmetric differential provenance ("bad - good"; DESIGN.md §Symmetric diff) ----
+// Entry e walks its own graph (failed run e's raw post graph) against run 0's
+// post-goal label hash: one launch over all entries, on the context's stream,
+// in call order.  Results stay in HBM until fetched; the state is disjoint
+// from nemo_diffprov's.
+int nemo_diffprov_symmetric(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed) {
+  if (c && c->node)
+    return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric: single-device contexts only (a node context does not fan it out)");
+  if (!c || (!failed_iters && n_failed)) return NEMO_ERR_INVALID;
+  if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric without a loaded corpus (the last load failed?)");
+  if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric before nemo_mark_holds");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cs.n_sentries = 0;
+  c->cs.sd_done = false;
+  c->cs.sd_graph.clear();
+  c->cs.sd_off.assign(1, 0);
+  if (n_failed == 0 || c->cs.run0 < 0) {  // nothing to compare with: zero entries, as nemo_diffprov
+    c->cs.sd_done = true;
+    return NEMO_OK;
+  }
+  if (n_failed > 0xFFFFFFFFull) return fail(c, NEMO_ERR_LIMIT, "too many diff entries");
+  std::vector<uint32_t> graph(n_failed);
+  std::vector<uint64_t> off(n_failed + 1, 0);
+  uint32_t n_lds = 0, n_glob = 0;
+  // algorithmic bytes per entry: rows both ways (8E + 8V), node word + label + Kahn order (12V),
+  // the mask written (V); the three sweeps are counted as traversed edges
+  double bytes = 0, edges = 0;
+  int rc;
+  for (size_t e = 0; e < n_failed; e++) {
+    uint32_t r;
+    if ((rc = run_index(c, failed_iters[e], &r))) return rc;
+    const uint32_t g = 2 * r + 1;
+    const uint64_t V = c->cs.node_off[g + 1] - c->cs.node_off[g], E = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+    graph[e] = g;
+    off[e + 1] = off[e] + V;
+    if (tier_fits(c->cs.dc.t_diff, (uint32_t)std::min<uint64_t>(V, ~0u), (uint32_t)std::min<uint64_t>(E, ~0u), 0)) n_lds++;
+    else n_glob++;
+    bytes += 8.0 * E + 21.0 * V;
+    edges += 3.0 * E;
+  }
+  const uint64_t total = off[n_failed];
+  const bool grow_v = total > c->cs.sd_vcap || !c->cs.d_sdmask, grow_b = n_glob && (total > c->cs.sd_bcap || !c->cs.d_sdbits);
+  if (n_failed > c->cs.sd_ecap || grow_v || grow_b) {
+    // an earlier symmetric call or its pull may still use the buffers
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_failed > c->cs.sd_ecap) {
+      dfree(c, c->cs.d_sdgraph);
+      dfree(c, c->cs.d_sdoff);
+      c->cs.d_sdgraph = nullptr;
+      c->cs.d_sdoff = nullptr;
+      c->cs.sd_ecap = 0;
+      const uint64_t cap = (n_failed + 63) & ~(uint64_t)63;
+      if ((rc = dalloc(c, &c->cs.d_sdgraph, cap))) return rc;
+      if ((rc = dalloc(c, &c->cs.d_sdoff, cap + 1))) return rc;
+      c->cs.sd_ecap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+    }
+    if (grow_v) {
+      for (void *q : {(void *)c->cs.d_sdmask, (void *)c->cs.d_sddepth, (void *)c->cs.d_sdrows, (void *)c->cs.d_sdbits}) dfree(c, q);
+      c->cs.d_sdmask = c->cs.d_sdbits = nullptr;
+      c->cs.d_sddepth = nullptr;
+      c->cs.d_sdrows = nullptr;
+      c->cs.sd_vcap = c->cs.sd_bcap = 0;
+      if ((rc = dalloc(c, &c->cs.d_sdmask, total))) return rc;
+      if ((rc = dalloc(c, &c->cs.d_sddepth, total))) return rc;
+      // a row per S rule at most, and the rules of all entries are at most their nodes: no overflow
+      if ((rc = dalloc(c, &c->cs.d_sdrows, 2 * total + 2))) return rc;
+      c->cs.sd_vcap = total;
+    }
+    if (grow_b || (n_glob && grow_v)) {  // node bits of the global tier only
+      dfree(c, c->cs.d_sdbits);
+      c->cs.d_sdbits = nullptr;
+      c->cs.sd_bcap = 0;
+      if ((rc = dalloc(c, &c->cs.d_sdbits, c->cs.sd_vcap))) return rc;
+      c->cs.sd_bcap = c->cs.sd_vcap;
+    }
+  }
+  if (!c->cs.d_sdn && (rc = dalloc(c, &c->cs.d_sdn, 1))) return rc;
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->cs.d_sdgraph, graph.data(), n_failed * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->cs.d_sdoff, off.data(), (n_failed + 1) * 8, hipMemcpyHostToDevice, s));
+  nemo::launch_zero(c->cs.d_sdn, 4, s);
+  nemo::SdiffArgs a{};
+  a.graph = c->cs.d_sdgraph;
+  a.off = c->cs.d_sdoff;
+  a.r0hkey = c->cs.d_r0hkey;
+  a.r0hmask = c->cs.r0hmask;
+  a.bits = c->cs.d_sdbits;
+  a.depth = c->cs.d_sddepth;
+  a.mask = c->cs.d_sdmask;
+  a.rows = c->cs.d_sdrows;
+  a.n_rows = c->cs.d_sdn;
+  if ((rc = timed(c, "k_sdiff", bytes, edges,
+                  [&] { nemo::launch_sdiff(c->cs.dc, a, (uint32_t)n_failed, n_lds, n_glob, s); })))
+    return rc;
+  c->cs.sd_graph = std::move(graph);
+  c->cs.sd_off = std::move(off);
+  c->cs.n_sentries = (uint32_t)n_failed;
+  c->cs.sd_done = true;
+  return NEMO_OK;
+}
+
+int nemo_fetch_sdiff_masks(nemo_ctx *c, uint64_t *off, uint8_t *out, uint64_t cap, uint64_t *n_used) {
+  if (!c) return NEMO_ERR_INVALID;
+  if (!c->cs.sd_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_sdiff_masks before nemo_diffprov_symmetric");
+  const uint64_t total = c->cs.sd_off.back();
+  if (n_used) *n_used = total;
+  if (off) memcpy(off, c->cs.sd_off.data(), c->cs.sd_off.size() * 8);
+  if (!out) return NEMO_OK;
+  if (cap < total) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (total) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->cs.d_sdmask, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NEMO_OK;
+}
+
+int nemo_fetch_surplus(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n_out) {
+  if (!c) return NEMO_ERR_INVALID;
+  if (!c->cs.sd_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_surplus before nemo_diffprov_symmetric");
+  uint32_t n = 0;
+  if (c->cs.n_sentries) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(&n, c->cs.d_sdn, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (n_out) *n_out = n;
+  if (!out) return NEMO_OK;
+  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (!n) return NEMO_OK;
+  std::vector<uint32_t> rows(2 * (size_t)n);
+  HIPCHK(c, hipMemcpyAsync(rows.data(), c->cs.d_sdrows, 8ull * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  sort_rows<2>(rows.data(), n);  // the device emits in any order: by (entry, rule)
+  for (uint32_t k = 0; k < n; k++) {
+    out[k].entry = rows[2 * k];
+    out[k].rule = rows[2 * k + 1];
+  }
+  return NEMO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,499 @@
+// ctx.h — struct nemo_ctx, by lifetime (Options, CorpusState, context resources), and
+// the helpers every entry point uses.  Private to the library's host side (api*.hip, node.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <chrono>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "device.h"
+#include "internal.h"
+#include "node.h"
+
+struct Agg {
+  uint64_t launches = 0;
+  double ms = 0, bytes = 0, edges = 0;
+};
+struct PendingEv {
+  std::string name;
+  hipEvent_t a, b;
+  double bytes, edges;
+};
+
+static int fail(nemo_ctx *c, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+
+#define HIPCHK(c, x)                                                                               \
+  do {                                                                                             \
+    hipError_t e_ = (x);                                                                           \
+    if (e_ != hipSuccess) return fail((c), NEMO_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_));     \
+  } while (0)
+
+#define DISPATCH(call)              \
+  do {                              \
+    if (c && c->node) return call; \
+  } while (0)
+
+// A pinned host buffer of the context: grow-only, exactly as large as the largest request so far.
+template <class T>
+struct Pinned {
+  T *p = nullptr;
+  uint64_t cap = 0;  // elements
+  int grow(nemo_ctx *c, uint64_t n) {
+    if (n <= cap && p) return NEMO_OK;
+    if (p) HIPCHK(c, hipHostFree(p));
+    p = nullptr;
+    cap = 0;
+    HIPCHK(c, hipHostMalloc((void **)&p, (n ? n : 1) * sizeof(T), hipHostMallocDefault));
+    cap = n;
+    return NEMO_OK;
+  }
+  void **slot() { return (void **)&p; }  // for nemo_ctx::pinned
+};
+
+// the pull's slot tables (offset, count per slot) and region cursor: one capacity, in slots
+struct PullHost {
+  Pinned<uint32_t> cnt;
+  Pinned<uint64_t> off;
+  Pinned<unsigned long long> cur;
+  uint64_t cap() const { return std::min(cnt.cap, off.cap); }
+  int grow(nemo_ctx *c, uint64_t slots) {
+    int rc;
+    if ((rc = cnt.grow(c, slots)) || (rc = off.grow(c, slots))) return rc;
+    return cur.grow(c, 1);
+  }
+};
+
+// nemo_set_option's values.  They outlive loads; some take effect at the next load only.
+struct Options {
+  uint32_t hcap_limit = 0xFFFFFFFFu, comp_limit = 0xFFFFFFFFu, build_limit = 0xFFFFFFFFu;
+  uint32_t lds_limit = 0xFFFFFFFFu;  // test knob: largest V of the LDS graph tier (0 = off)
+  uint64_t glob_min_v = 65536;       // graphs with V >= this take k_chains_glob (set before load)
+  uint32_t gblock_force = 0;         // global_block option (0 = by corpus shape)
+  uint32_t glob_block_force = 0;     // chains_glob_block option (0 = by the number of deep graphs)
+  bool glob_prep_off = false;        // chains_glob_prep option 0: k_chains_glob builds its own H* order (test knob)
+  bool topo_ell_off = true;          // topo_ell option 1: deep graphs' Kahn levels by k_topo_ell (measured slower
+                                     // at C5: 103 vs 84 ms per launch with its records; kept as an option, tested)
+  bool relax_off = true;             // option build_relax 1: k_build's Kahn levels by relaxation sweeps first
+                                     // (measured slower at C3: k_build 2.96 -> 3.20 ms; kept as an option, tested)
+  bool ms_fuse_off = true;           // option build_marksimp 1: k_build's marksimp tail (measured slower at C3:
+                                     // k_build 3.00 -> 3.86 ms against k_marksimp's 0.80 ms; four workgroups
+                                     // per CU by k_build's LDS image where k_marksimp runs eight waves per SIMD)
+  uint32_t load_parts = 4;           // big-graph corpora upload in this many parts (nemo_load_corpus)
+  bool load_async = false;           // nemo_load_corpus returns once its work is queued
+  bool diff_on_aux = true;           // diff kernels on `aux` beside the simplification (option diff_aux)
+  int diff_legacy = 0;               // one workgroup per entry (k_diff.hip)
+  uint32_t diff_window = 0;          // test knob: 0 by size, 1 windowed, 2 tiny windows
+  uint32_t diff_unfused = 0;         // option diff_fuse 0 (test knob): whole-graph walks hand LP rules to k_dx_lp / k_dx_emit
+  // the simplified pull on `aux` (option pull_aux 1; off by default: beside k_proto_lds it made
+  // the C3 step 8.3 -> 9.0 ms)
+  uint32_t pull_on_aux = 0;
+  uint32_t stage_on_aux = 1;  // the hand-over kernels of nemo_stage_simplified on `aux` (option stage_aux)
+  uint32_t stage_blocks = 0;  // bulk staging: 0 = runtime copies, else k_to_host on this many blocks
+  bool stage_sdma = false;    // runtime copies requested as NoCU (SDMA) copies (cleared if the runtime refuses)
+  uint32_t stage_cus = 8;     // CUs of the copy stream (hipExtStreamCreateWithCUMask); 0 = unmasked
+};
+
+// Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
+// default initialiser is its value with no corpus loaded.  Device pointers point into nemo_ctx::allocs.
+struct CorpusState {
+  // host view
+  bool loaded = false, marked = false, simplified = false, protos_done = false;
+  uint32_t n_runs = 0, G = 0, T = 0, W = 0, table_pre = 0, table_post = 0;
+  uint64_t V = 0, E = 0;
+  std::vector<uint32_t> iteration;
+  std::vector<uint8_t> owned;
+  std::vector<uint64_t> node_off, edge_off;
+  std::unordered_map<uint32_t, uint32_t> it2run;
+  int32_t run0 = -1;
+  bool has_rank = false;
+  bool pairs_wide = false;           // some graph has >= 65536 nodes: u32 chain pairs
+  double tierV = 0, tierE = 0;       // nodes / edges of the graphs within the tier's V/E caps
+  uint32_t ms_rest = 0, pull_rest = 0;  // graphs past k_marksimp's / k_pull_lds's tiers (their global grids skipped at 0)
+  double postV = 0, postE = 0;       // nodes / edges of the post graphs (k_proto's input)
+  double bigV = 0, bigE = 0;         // nodes / edges of the graphs of >= NEMO_CSR_BIG nodes
+  uint64_t bigVmax = 0;              // the largest of them
+  uint32_t big_chunks = 1;           // k_csrb_* workgroups per big graph
+  std::vector<uint32_t> big_host;    // the big-graph list (DevCorpus::big) on the host
+  bool load_check_pending = false;   // option load_async: the graph checks wait for the next call that reads the graphs
+  bool mark_pending = false;         // holds flags of the tier graphs not yet computed
+  bool ms_fused = false;             // k_build's tail wrote its graphs' final flags at the last load / rebuild,
+                                     // not yet consumed by nemo_simplify (k_marksimp skips those graphs)
+
+  DevCorpus dc{};
+  uint8_t *d_owned = nullptr, *d_is_success = nullptr;
+  uint32_t *d_red = nullptr;
+  const uint32_t *red_staged = nullptr;  // nemo_protos_stage's vector, copied into h_red behind ev_red
+
+  // The global tiers' worklist sizes [load (k_csr/k_topo), chains (k_chains_list/_big), protos
+  // (k_pg_*)] of the last full pass.  They are functions of the loaded corpus and the options
+  // alone (sizes, Kahn level counts, in-degree caps, chain counts: every pass recomputes the
+  // same), so once a pass's counts are known an empty tier is not launched at all (each of its
+  // ~10 empty launches cost ~6 us on the analysis stream).  Reset by a load and by any option.
+  bool tiers_pending = false, tiers_ok = false;
+  uint32_t tiers[3] = {0, 0, 0}, tiers_run = 0;
+
+  // diff
+  uint32_t n_entries = 0, diff_cap = 0, legacy_cap = 0;
+  uint32_t *d_r0lab = nullptr, *d_r0idx = nullptr, n_r0lab = 0;
+  uint32_t *d_r0hkey = nullptr, *d_r0hval = nullptr, r0hmask = 0;
+  uint32_t *d_r0dense = nullptr, nlab = 0;  // the dense label table of the multi-entry diff (DxArgs::r0dense)
+  uint32_t *d_dsrc = nullptr, *d_miss = nullptr, *d_nmiss = nullptr;
+  uint8_t *d_dbits = nullptr, *d_dmask = nullptr;
+  int32_t *d_ddepth = nullptr;
+  uint32_t *d_dtopo = nullptr;       // g0 in Kahn order (DiffArgs::tpos ...)
+  uint64_t mrows_staged = 0;         // missing rows copied with the D masks
+  // entries that share a label source share one computation: n_uniq distinct
+  // sources, entry e's result is unique result dmap[e] (d_dmap on the device)
+  uint32_t n_uniq = 0, *d_dmap = nullptr;
+  uint8_t *d_dumask = nullptr;       // [n_uniq * V0] when n_uniq < n_entries
+  std::vector<uint32_t> dmap;
+  bool aux_pending = false;          // diff kernels queued on `aux` that `stream` has not joined (join_aux)
+  // the multi-entry diff (k_dx.hip): g0's Kahn-order relayout, built with the
+  // CSR in every load / rebuild, and the per-call buffers (grow-only)
+  nemo::DxPrep dxp{};
+  nemo::DxImg dx_img[2]{};           // walk images of g0 (k_dx.hip), built for the test knob dx_img_key
+  nemo::DxImgScratch dx_its{};
+  int dx_img_key = -1;               // -1: not built for the current load
+  bool dx_ok = false;                // relayout allocated: run 0 present, every row fits a window
+  uint32_t g0_maxdeg = 0;
+  uint32_t dx_nu_cap = 0, dx_nch_cap = 0;
+  uint32_t *d_dxpb = nullptr, *d_dxsval = nullptr, *d_dxlpl = nullptr, *d_dxfb = nullptr;
+  uint64_t *d_dxw = nullptr;  // [4][nch][V0] Good / LP, B, D, leaf candidates
+  bool dx_last = false;              // the last diffprov ran the multi-entry kernels
+  uint32_t *d_hlab = nullptr;        // nemo_diffprov_host_labels' set [n, label...]
+  uint64_t hlab_cap = 0;
+
+  // symmetric diff (k_sdiff.hip): all of it the call's own state, so that a symmetric call leaves
+  // the results of a previous nemo_diffprov alone and the reverse; buffers grow only
+  bool sd_done = false;              // a symmetric call completed on the loaded corpus (n_sentries may be 0)
+  uint32_t n_sentries = 0, sd_ecap = 0;
+  uint64_t sd_vcap = 0, sd_bcap = 0;  // nodes the ragged buffers / the global tier's bits hold
+  std::vector<uint32_t> sd_graph;    // entry -> its failed post graph
+  std::vector<uint64_t> sd_off;      // [n + 1] entry -> first node of its slices
+  uint32_t *d_sdgraph = nullptr, *d_sdrows = nullptr, *d_sdn = nullptr;
+  uint64_t *d_sdoff = nullptr;
+  uint8_t *d_sdmask = nullptr, *d_sdbits = nullptr;
+  int32_t *d_sddepth = nullptr;
+
+  // pulls: per-slot (offset, count) and the region cursor come back to pinned
+  // memory asynchronously; the first fetch waits for them
+  int pull_which = -1;
+  uint32_t pull_slots = 0, pull_slot_cap = 0;
+  uint32_t pull_dslots = 0;              // slots computed: diff entries sharing a label source share one
+  std::vector<uint32_t> pull_map;        // which 2 with shared slots: entry -> computed slot
+  uint32_t *d_pck = nullptr;          // big graphs' pull chunk table
+  size_t pull_ck_cap = 0;
+  uint32_t *d_pcnt = nullptr, *d_psrc = nullptr, *d_pdst = nullptr;
+  uint64_t *d_poff = nullptr, pull_cap = 0;
+  unsigned long long *d_pcur = nullptr;
+  bool pull_synced = true;
+  bool pull_aux_pending = false;      // a pull on `aux` not yet joined by `stream` (guard_staged)
+  uint64_t pull_hint[4] = {0, 0, 0, 0};
+  nemo::PullArgs pull_args{};
+
+  // triggers: outputs sized at load from run 0's degrees (exact bounds), one
+  // launch; the row counts come back to pinned memory asynchronously
+  bool trig_done = false, trig_pending = false;
+  uint32_t *d_tcounts = nullptr, *d_tpre = nullptr, *d_tpost = nullptr, *d_tasync = nullptr;
+  uint32_t tcounts[3] = {0, 0, 0};
+  uint64_t tcap[3] = {0, 0, 0};
+
+  // chain gather
+  uint32_t *d_chout = nullptr;
+  uint64_t *d_choff = nullptr, chout_cap = 0;
+
+  // staged simplification results
+  bool flags_final = false;  // ev_flags marks the current flags (no flag-rewriting call since)
+  hipStream_t stage_stream = nullptr;  // the stream the last stage's hand-over kernels went on
+  bool staged = false;
+  uint64_t staged_n = 0, staged_cap = 0, chht_hint = 0;
+  uint32_t *d_state = nullptr;  // 2-bit node state (k_pack_state)
+  uint32_t *d_chht = nullptr;
+  uint64_t d_chht_cap = 0;
+};
+
+struct nemo_ctx {
+  Node *node = nullptr;  // node context: every entry point dispatches to node.hip
+  int device = 0;
+  Options opt;
+  CorpusState cs;
+  std::string err;
+
+  // streams: `stream` is the caller's (nemo_set_stream) or `own`; the others are created at first use
+  hipStream_t own = nullptr, stream = nullptr;
+  // uploads of a corpus of big graphs, in parts, so that the CSR build of part k overlaps the
+  // upload of part k + 1 (nemo_load_corpus; option load_parts)
+  hipStream_t up = nullptr;
+  // CreateNaiveDiffProv reads only the raw run-0 graph and the label sources
+  // (differential-provenance.go:22-98), so its kernels run on `aux`, beside
+  // the simplification on `stream`; whatever rewrites the graphs' structure,
+  // or reads the D masks on `stream`, first waits for ev_diff (join_aux)
+  hipStream_t aux = nullptr;
+  hipStream_t copy = nullptr;  // staged simplification results: pinned host copies made on `copy`
+  hipStream_t *const streams[4] = {&copy, &up, &aux, &own};  // the context's own, in nemo_ctx_destroy's order
+
+  // named events, created by ensure_event at first use
+  hipEvent_t ev_fork = nullptr, ev_pull = nullptr, ev_trig = nullptr;
+  hipEvent_t ev_protos = nullptr, ev_red = nullptr, ev_diff = nullptr, ev_misc = nullptr, ev_tiers = nullptr;
+  // pinned upload staging is reused once the previous upload from the same buffer has landed
+  hipEvent_t ev_up_hlab = nullptr, ev_up_succ = nullptr, ev_up_dsrc = nullptr;
+  hipEvent_t ev_ready = nullptr, ev_copied = nullptr;
+  // a simplified pull on `aux` waits for the end of nemo_simplify (ev_simp) only, so it runs
+  // beside the protos and hand-over kernels of `stream`; anything that rewrites its inputs
+  // first waits for ev_auxpull
+  hipEvent_t ev_simp = nullptr, ev_auxpull = nullptr;
+  // recorded by nemo_simplify once the node flags are final (after the mark / clean / delete-set
+  // kernels, before the chain cover, which only reads them): the staged 2-bit node state is
+  // packed and copied from there on, beside the chain cover (nemo_stage_simplified)
+  hipEvent_t ev_flags = nullptr, ev_state = nullptr;
+  // the hand-over kernels of nemo_stage_simplified on `aux`: behind everything `stream` has
+  // queued so far, beside the triggers and pulls queued after
+  hipEvent_t ev_stage = nullptr;
+  hipEvent_t *const events[18] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+                                  &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
+                                  &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage};
+  std::vector<hipEvent_t> ev_up;  // one per upload part
+
+  // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
+  Pinned<uint32_t> h_red, h_tab, h_nmiss, h_mrows, h_tpre, h_tpost, h_tasync, h_tcounts, h_tiers;
+  Pinned<uint8_t> h_mask, h_succ, h_flags;
+  Pinned<uint32_t> h_hlab, h_dsrc, h_chht;
+  Pinned<uint64_t> h_choff;
+  PullHost h_pull;
+  void **const pinned[19] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+                             h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
+                             h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
+                             h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot()};
+  // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
+  // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
+  uint64_t mrows_hint = 256;
+
+  // device blocks: `allocs` are the loaded corpus's, `cache` the previous corpus's, kept for the
+  // next load (nemo_load_corpus frees what it did not reuse): reloading a corpus of the same
+  // shape allocates nothing
+  std::vector<void *> allocs;
+  std::unordered_map<void *, size_t> alloc_bytes;  // every live allocation's size (allocs and the cache)
+  std::multimap<size_t, void *> cache;
+  // NEMO_LOAD_DEBUG: dalloc calls since the load began and a running hash of their sizes in order
+  uint64_t dalloc_n = 0, dalloc_hash = 0;
+
+  // per-kernel timing
+  std::vector<std::string> tgroups;  // nemo_set_timing_groups: the timed groups (empty: all)
+  bool timing = false;
+  std::vector<PendingEv> pending;
+  std::vector<hipEvent_t> ev_pool;
+  std::map<std::string, Agg> agg;
+};
+
+static inline int fail(nemo_ctx *c, int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (c) c->err = buf;
+  return code;
+}
+
+// the cached blocks (nemo_ctx::cache)
+static inline void drop_cache(nemo_ctx *c) {
+  for (auto &b : c->cache) {
+    c->alloc_bytes.erase(b.second);
+    hipFree(b.second);
+  }
+  c->cache.clear();
+}
+
+template <class T>
+static int dalloc(nemo_ctx *c, T **p, size_t n) {
+  void *q = nullptr;
+  if (n == 0) n = 1;
+  // whole 16-byte chunks: stage_lds (device.h) loads aligned 16-B chunks, so
+  // the chunk holding a buffer's last byte must lie inside the allocation
+  const size_t bytes = (n * sizeof(T) + 15) & ~(size_t)15;
+  c->dalloc_n++;
+  c->dalloc_hash = (c->dalloc_hash ^ bytes) * 0x100000001B3ull;  // the request order decides who gets which cached block
+  auto it = c->cache.lower_bound(bytes);  // the smallest cached block that fits, if not much larger
+  if (it != c->cache.end() && it->first <= bytes + bytes / 8 + (1u << 20)) {
+    q = it->second;
+    c->cache.erase(it);
+  } else {
+    // large blocks get headroom, so that the next corpus of about the same shape reuses them: 1/16
+    // (C5's 143-run batches differ by up to 3.3 % in edges; at 1/32 a load found some block too small
+    // about every other time, allocated anew (~28 ms) and the next load's drop_cache freed the unused
+    // block: hipFree waits for the whole device, ~220 ms behind the other context's analysis)
+    const size_t want = bytes >= (64u << 20) ? ((bytes + bytes / 16) + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1) : bytes;
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t e = hipMalloc(&q, want);
+    if (getenv("NEMO_LOAD_DEBUG") && want >= (64u << 20))
+      fprintf(stderr, "dalloc: new block %zu MB (%s) %.1f ms, %zu cached\n", want >> 20, e == hipSuccess ? "ok" : "failed",
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), c->cache.size());
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      drop_cache(c);  // no room: the cached blocks go first, then the headroom
+      e = hipMalloc(&q, bytes);
+      if (e != hipSuccess) return fail(c, NEMO_ERR_HIP, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+      c->alloc_bytes[q] = bytes;
+    } else {
+      c->alloc_bytes[q] = want;
+    }
+  }
+  c->allocs.push_back(q);
+  *p = (T *)q;
+  return NEMO_OK;
+}
+
+static inline void dfree(nemo_ctx *c, void *p) {
+  if (!p) return;
+  auto it = std::find(c->allocs.begin(), c->allocs.end(), p);
+  if (it != c->allocs.end()) c->allocs.erase(it);
+  c->alloc_bytes.erase(p);
+  hipFree(p);
+}
+
+static inline hipEvent_t get_event(nemo_ctx *c) {
+  if (!c->ev_pool.empty()) {
+    hipEvent_t e = c->ev_pool.back();
+    c->ev_pool.pop_back();
+    return e;
+  }
+  hipEvent_t e = nullptr;
+  hipEventCreate(&e);
+  return e;
+}
+
+static inline int ensure_event(nemo_ctx *c, hipEvent_t *e) {
+  if (!*e) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+  return NEMO_OK;
+}
+
+// Kernels that rewrite node flags must not overtake a staged copy still in flight.
+static inline int guard_staged(nemo_ctx *c) {
+  c->cs.flags_final = false;  // the caller is about to rewrite node flags
+  if (c->cs.staged) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied, 0));
+  if (c->cs.pull_aux_pending) {  // a pull on `aux` still reads the graphs, flags and chains
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_auxpull, 0));
+    c->cs.pull_aux_pending = false;
+  }
+  return NEMO_OK;
+}
+
+// the finished timed launches into `agg`; their events go back to the pool
+static inline int collect_timings(nemo_ctx *c) {
+  for (auto &p : c->pending) {
+    HIPCHK(c, hipEventSynchronize(p.b));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, p.a, p.b));
+    Agg &g = c->agg[p.name];
+    g.launches++;
+    g.ms += ms;
+    g.bytes += p.bytes;
+    g.edges += p.edges;
+    c->ev_pool.push_back(p.a);
+    c->ev_pool.push_back(p.b);
+  }
+  c->pending.clear();
+  return NEMO_OK;
+}
+
+template <class F>
+static int timed_on(nemo_ctx *c, hipStream_t st, const char *name, double bytes, double edges, F &&f) {
+  hipEvent_t a = nullptr, b = nullptr;
+  const bool timed = c->timing && (c->tgroups.empty() ||
+                                   std::find(c->tgroups.begin(), c->tgroups.end(), name) != c->tgroups.end());
+  if (timed) {
+    a = get_event(c);
+    b = get_event(c);
+    hipEventRecord(a, st);
+  }
+  f();
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(c, NEMO_ERR_HIP, "launch %s: %s", name, hipGetErrorString(e));
+  if (timed) {
+    hipEventRecord(b, st);
+    c->pending.push_back({name, a, b, bytes, edges});
+    if (c->pending.size() > 4096) collect_timings(c);  // bound outstanding events (they may be on two streams)
+  }
+  return NEMO_OK;
+}
+
+template <class F>
+static int timed(nemo_ctx *c, const char *name, double bytes, double edges, F &&f) {
+  return timed_on(c, c->stream, name, bytes, edges, f);
+}
+
+// `stream` waits for the diff kernels queued on `aux` (see nemo_ctx::aux)
+static inline int join_aux(nemo_ctx *c) {
+  if (!c->cs.aux_pending) return NEMO_OK;
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_diff, 0));
+  c->cs.aux_pending = false;
+  return NEMO_OK;
+}
+
+static inline int run_index(nemo_ctx *c, uint32_t it, uint32_t *r) {
+  auto f = c->cs.it2run.find(it);
+  if (f == c->cs.it2run.end()) return fail(c, NEMO_ERR_NOTFOUND, "unknown run iteration %u", it);
+  *r = f->second;
+  return NEMO_OK;
+}
+
+template <int K>
+static void sort_rows(uint32_t *rows, uint64_t n) {
+  std::vector<std::array<uint32_t, K>> v(n);
+  for (uint64_t i = 0; i < n; i++)
+    for (int k = 0; k < K; k++) v[i][k] = rows[K * i + k];
+  std::sort(v.begin(), v.end());
+  for (uint64_t i = 0; i < n; i++)
+    for (int k = 0; k < K; k++) rows[K * i + k] = v[i][k];
+}
+
+static inline int check_graph_errors(nemo_ctx *c) {
+  std::vector<uint32_t> err(c->cs.G), created(c->cs.G);
+  HIPCHK(c, hipMemcpyAsync(err.data(), c->cs.dc.err, c->cs.G * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(created.data(), c->cs.dc.created, c->cs.G * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (uint32_t g = 0; g < c->cs.G; g++) {
+    if (!err[g]) continue;
+    const uint32_t it = c->cs.iteration[g / 2];
+    const uint64_t E = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+    if (err[g] == NEMO_ERR_LOAD)
+      return fail(c, NEMO_ERR_LOAD,
+                  "Run %u: inserted number of edges (%u) does not equal number of antecedent provenance edges (%llu)",
+                  it, created[g], (unsigned long long)E);
+    if (err[g] == NEMO_ERR_CYCLE) return fail(c, NEMO_ERR_CYCLE, "Run %u: provenance graph is not acyclic", it);
+    return fail(c, (int)err[g], "Run %u: edge references a node index out of range", it);
+  }
+  return NEMO_OK;
+}
+
+// Option load_async: the last load's graph checks (validations, acyclicity), before the first call
+// that reads its graphs; a failed check leaves no corpus loaded, as a failed nemo_load_corpus does.
+static inline int ensure_load_checked(nemo_ctx *c) {
+  if (!c->cs.load_check_pending) return NEMO_OK;
+  c->cs.load_check_pending = false;
+  const int rc = check_graph_errors(c);
+  if (rc) c->cs.loaded = false;
+  return rc;
+}
+
+// markConditionHolds is deferred for the LDS-tier graphs: nemo_simplify runs
+// it fused with the simplification (k_marksimp).  Anything that reads the
+// holds flags before that materialises it first (ensure_marked).
+static inline int ensure_marked(nemo_ctx *c) {
+  if (!c->cs.mark_pending) return NEMO_OK;
+  const double V = c->cs.tierV, E = c->cs.tierE;
+  int rc = timed(c, "k_mark", 8 * E + 13 * V, 2 * E, [&] { nemo::launch_mark(c->cs.dc, false, c->stream); });
+  if (rc) return rc;
+  c->cs.mark_pending = false;
+  c->cs.ms_fused = false;  // k_mark rewrote every graph's flags (holds only)
+  return NEMO_OK;
+}

@@ -7,15 +7,9 @@
 
 struct Node;
 
-// api.hip: accessors of a context that node.hip drives through the public ABI
-Node *ctx_node(const nemo_ctx *c);
-nemo_ctx *ctx_new_facade(Node *n);  // a context whose every entry point dispatches to `n`
+// api.hip: a context whose every entry point dispatches to `n` (nemo_ctx::node)
+nemo_ctx *ctx_new_facade(Node *n);
 void ctx_delete_facade(nemo_ctx *c);
-int ctx_fail(nemo_ctx *c, int code, const char *msg);
-uint32_t *ctx_reduce_buf(nemo_ctx *c);  // the context's own reduction vector (device)
-hipStream_t ctx_stream(nemo_ctx *c);
-int ctx_device(const nemo_ctx *c);
-int ctx_join_aux(nemo_ctx *c);  // the context's stream waits for its queued diff kernels
 
 // node.hip: the node context's entry points (same contracts as nemohip.h)
 void node_destroy(Node *n);

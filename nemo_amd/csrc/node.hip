@@ -37,7 +37,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "node.h"
+#include "ctx.h"
 
 namespace {
 
@@ -142,20 +142,10 @@ struct Node {
   bool wide = false;
 };
 
-static int fail(nemo_ctx *c, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-static int fail(nemo_ctx *c, int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return ctx_fail(c, code, buf);
-}
-
 // a shard's failure, reported by the node context with the shard's message
 static int sfail(nemo_ctx *c, const Shard &s, int rc) {
   std::string m = std::string("device ") + std::to_string(s.device) + ": " + nemo_last_error(s.ctx);
-  return ctx_fail(c, rc, m.c_str());
+  return fail(c, rc, "%s", m.c_str());
 }
 
 #define SCHK(c, s, x)                  \
@@ -182,7 +172,7 @@ __global__ void k_sum_u32(uint32_t *acc, const uint32_t *parts, uint32_t n_parts
   }
 }
 
-static Node *N(const nemo_ctx *c) { return ctx_node(c); }
+static Node *N(const nemo_ctx *c) { return c ? c->node : nullptr; }
 
 // f(shard, p) on every shard, one host thread per shard; the first failing
 // shard's status and message are reported
@@ -246,7 +236,7 @@ extern "C" int nemo_ctx_create_node(int ndev, const int *devices, nemo_ctx **out
 extern "C" int nemo_node_devices(const nemo_ctx *c, int *devices, int cap) {
   const Node *n = c ? N(c) : nullptr;
   if (!n) {  // a single-device context
-    if (c && devices && cap > 0) devices[0] = ctx_device(c);
+    if (c && devices && cap > 0) devices[0] = c->device;
     return c ? 1 : 0;
   }
   for (int i = 0; i < (int)n->sh.size() && devices && i < cap; i++) devices[i] = n->sh[i].device;
@@ -439,15 +429,15 @@ static int allreduce_sum(nemo_ctx *c, Node *n, uint64_t len) {
   if (n->rccl) {
     NCHK(c, ncclGroupStart());
     for (size_t p = 0; p < P; p++) {
-      uint32_t *d = ctx_reduce_buf(n->sh[p].ctx);
-      NCHK(c, ncclAllReduce(d, d, len, ncclUint32, ncclSum, n->comms[p], ctx_stream(n->sh[p].ctx)));
+      uint32_t *d = n->sh[p].ctx->cs.d_red;
+      NCHK(c, ncclAllReduce(d, d, len, ncclUint32, ncclSum, n->comms[p], n->sh[p].ctx->stream));
     }
     NCHK(c, ncclGroupEnd());
     return NEMO_OK;
   }
   // peer copies into shard 0, one sum kernel, copies back
   Shard &s0 = n->sh[0];
-  hipStream_t st0 = ctx_stream(s0.ctx);
+  hipStream_t st0 = s0.ctx->stream;
   HCHK(c, hipSetDevice(s0.device));
   if (n->tmp_cap < (P - 1) * len) {
     if (n->d_tmp) HCHK(c, hipFree(n->d_tmp));
@@ -457,21 +447,21 @@ static int allreduce_sum(nemo_ctx *c, Node *n, uint64_t len) {
   }
   for (size_t p = 1; p < P; p++) {
     HCHK(c, hipSetDevice(n->sh[p].device));
-    HCHK(c, hipEventRecord(n->ev[p], ctx_stream(n->sh[p].ctx)));
+    HCHK(c, hipEventRecord(n->ev[p], n->sh[p].ctx->stream));
     HCHK(c, hipSetDevice(s0.device));
     HCHK(c, hipStreamWaitEvent(st0, n->ev[p], 0));
-    HCHK(c, hipMemcpyPeerAsync(n->d_tmp + (p - 1) * len, s0.device, ctx_reduce_buf(n->sh[p].ctx), n->sh[p].device,
+    HCHK(c, hipMemcpyPeerAsync(n->d_tmp + (p - 1) * len, s0.device, n->sh[p].ctx->cs.d_red, n->sh[p].device,
                                len * 4, st0));
   }
-  hipLaunchKernelGGL(k_sum_u32, dim3(16), dim3(256), 0, st0, ctx_reduce_buf(s0.ctx), n->d_tmp, (uint32_t)(P - 1), len);
+  hipLaunchKernelGGL(k_sum_u32, dim3(16), dim3(256), 0, st0, s0.ctx->cs.d_red, n->d_tmp, (uint32_t)(P - 1), len);
   HCHK(c, hipGetLastError());
   for (size_t p = 1; p < P; p++)
-    HCHK(c, hipMemcpyPeerAsync(ctx_reduce_buf(n->sh[p].ctx), n->sh[p].device, ctx_reduce_buf(s0.ctx), s0.device, len * 4,
+    HCHK(c, hipMemcpyPeerAsync(n->sh[p].ctx->cs.d_red, n->sh[p].device, s0.ctx->cs.d_red, s0.device, len * 4,
                                st0));
   HCHK(c, hipEventRecord(n->ev[0], st0));
   for (size_t p = 1; p < P; p++) {
     HCHK(c, hipSetDevice(n->sh[p].device));
-    HCHK(c, hipStreamWaitEvent(ctx_stream(n->sh[p].ctx), n->ev[0], 0));
+    HCHK(c, hipStreamWaitEvent(n->sh[p].ctx->stream, n->ev[0], 0));
   }
   return NEMO_OK;
 }
@@ -484,18 +474,18 @@ static int broadcast_labels(nemo_ctx *c, Node *n, uint32_t root, uint64_t count)
     NCHK(c, ncclGroupStart());
     for (size_t p = 0; p < P; p++)
       NCHK(c, ncclBroadcast(n->sh[p].d_lab, n->sh[p].d_lab, count, ncclUint32, (int)root, n->comms[p],
-                            ctx_stream(n->sh[p].ctx)));
+                            n->sh[p].ctx->stream));
     NCHK(c, ncclGroupEnd());
     return NEMO_OK;
   }
   Shard &o = n->sh[root];
-  hipStream_t so = ctx_stream(o.ctx);
+  hipStream_t so = o.ctx->stream;
   // a destination's d_lab may still be read by its previous k_diff: the copy
   // waits for everything queued on that shard's stream so far
   for (size_t p = 0; p < P; p++) {
     if (p == root) continue;
     HCHK(c, hipSetDevice(n->sh[p].device));
-    HCHK(c, hipEventRecord(n->ev[p], ctx_stream(n->sh[p].ctx)));
+    HCHK(c, hipEventRecord(n->ev[p], n->sh[p].ctx->stream));
     HCHK(c, hipSetDevice(o.device));
     HCHK(c, hipStreamWaitEvent(so, n->ev[p], 0));
   }
@@ -506,7 +496,7 @@ static int broadcast_labels(nemo_ctx *c, Node *n, uint32_t root, uint64_t count)
   for (size_t p = 0; p < P; p++) {
     if (p == root) continue;
     HCHK(c, hipSetDevice(n->sh[p].device));
-    HCHK(c, hipStreamWaitEvent(ctx_stream(n->sh[p].ctx), n->ev[root], 0));
+    HCHK(c, hipStreamWaitEvent(n->sh[p].ctx->stream, n->ev[root], 0));
   }
   return NEMO_OK;
 }
@@ -615,7 +605,7 @@ static int node_diff(nemo_ctx *c, const uint32_t *failed, size_t nf, int mode, c
     }
   // every shard's stream first waits for its previous diff (on the shard's aux
   // stream), which may still read the d_lab this broadcast overwrites
-  for (auto &s : n->sh) SCHK(c, s, ctx_join_aux(s.ctx));
+  for (auto &s : n->sh) SCHK(c, s, join_aux(s.ctx));
   SCHK(c, n->sh[root], nemo_goal_labels(n->sh[root].ctx, failed[0], 1, n->sh[root].d_lab, cap));
   if (int rc = broadcast_labels(c, n, root, cap)) return rc;
   return fanout(c, n, [&](Shard &s, size_t p) {
