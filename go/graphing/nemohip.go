@@ -571,6 +571,77 @@ func (n *Neo4J) CreateNaiveDiffProv(symmetric bool, failedRuns []uint, successPo
 	return diffDots, failedDots, missing, nil
 }
 
+// FailureClass is one distinct failure mode among the failed runs: the runs
+// whose differential provenance against the good run is the same graph.
+type FailureClass struct {
+	Representative uint          // iteration of the class's first failed run
+	Members        []uint        // iterations of every member, in failedRuns order
+	Nodes          uint          // nodes of the differential provenance
+	Missing        []*fi.Missing // the representative's missing events
+	Diff           *gographviz.Graph
+}
+
+// FailureClasses has no reference counterpart: it summarises what
+// CreateNaiveDiffProv (differential-provenance.go:18-146) returns per failed run.
+// The library groups the diff entries by identical D mask on the device
+// (nemo_diff_classes); the missing events and the diff DOT are then built once
+// per class, for its representative, by CreateNaiveDiffProv.  Largest class
+// first, ties by representative.  Support[v] counts the failed runs whose
+// differential provenance holds node v of the good run's post graph.
+func (n *Neo4J) FailureClasses(failedRuns []uint, successPostProv *gographviz.Graph) ([]*FailureClass, []uint32, error) {
+	f := make([]C.uint32_t, len(failedRuns)+1)
+	for i, it := range failedRuns {
+		f[i] = C.uint32_t(it)
+	}
+	if err := n.err(C.nemo_diffprov(n.ctx, &f[0], C.size_t(len(failedRuns)), C.NEMO_DIFF_REFERENCE)); err != nil {
+		return nil, nil, err
+	}
+	if err := n.err(C.nemo_diff_classes(n.ctx)); err != nil {
+		return nil, nil, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_diff_classes(n.ctx, nil, nil, 0, &cnt)); err != nil {
+		return nil, nil, err
+	}
+	classOf := make([]C.uint32_t, len(failedRuns)+1)
+	classes := make([]C.nemo_diff_class, cnt+1)
+	if err := n.err(C.nemo_fetch_diff_classes(n.ctx, &classOf[0], &classes[0], cnt, &cnt)); err != nil {
+		return nil, nil, err
+	}
+	V0 := n.graphs[2*n.runIdx[0]+1].n()
+	sup := make([]C.uint32_t, V0+1)
+	if err := n.err(C.nemo_fetch_diff_support(n.ctx, &sup[0], C.uint64_t(V0))); err != nil {
+		return nil, nil, err
+	}
+	support := make([]uint32, V0)
+	for v := range support {
+		support[v] = uint32(sup[v])
+	}
+	out := make([]*FailureClass, cnt)
+	for k := range out {
+		dc := classes[k]
+		out[k] = &FailureClass{Representative: failedRuns[dc.rep], Nodes: uint(dc.nodes)}
+	}
+	for e, it := range failedRuns {
+		if len(out) > 0 {
+			out[classOf[e]].Members = append(out[classOf[e]].Members, it)
+		}
+	}
+	sort.SliceStable(out, func(a, b int) bool { return len(out[a].Members) > len(out[b].Members) })
+	reps := make([]uint, len(out))
+	for k, fc := range out {
+		reps[k] = fc.Representative
+	}
+	diffs, _, missing, err := n.CreateNaiveDiffProv(false, reps, successPostProv)
+	if err != nil {
+		return nil, nil, err
+	}
+	for k, fc := range out {
+		fc.Diff, fc.Missing = diffs[k], missing[k]
+	}
+	return out, support, nil
+}
+
 func (n *Neo4J) childrenOf(g int) map[uint32][]uint32 {
 	s, d := n.graphs[g].src, n.graphs[g].dst
 	ch := map[uint32][]uint32{}

@@ -188,7 +188,12 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       in registers, peeling if they give up (1), or by peeling
  *                       (0, default)
  *   "topo_ell"          deep graphs' Kahn levels by the edge-parallel k_topo_ell
- *                       (1) or one workgroup per graph, k_topo_deep (0, default) */
+ *                       (1) or one workgroup per graph, k_topo_deep (0, default)
+ *   "class_hash_bits"   nemo_diff_classes buckets the D masks by the low k bits of
+ *                       their 128-bit hash, k in 0..128 (default 128); every
+ *                       bucket is verified by exact row comparisons, so fewer bits
+ *                       only force collisions and more comparison rounds (test
+ *                       knob; at 0 every mask collides with every other) */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -296,6 +301,37 @@ int nemo_fetch_diff_masks(nemo_ctx *ctx, uint8_t *out, uint64_t cap);
 int nemo_diff_masks_view(nemo_ctx *ctx, const uint8_t **masks, uint64_t *n_entries, uint64_t *v0);
 /* Missing rules of every entry; goals = all D-children of each rule.        */
 int nemo_fetch_missing(nemo_ctx *ctx, nemo_missing *out, uint64_t cap, uint64_t *n_out);
+
+/* ---- failure classes: diff entries grouped by identical D mask ---------------
+ * Replaces nothing in the reference: the calls summarise the output of
+ * CreateNaiveDiffProv (differential-provenance.go:18-146), which returns one
+ * diff graph and one set of missing events per failed run and leaves "which
+ * runs failed the same way" to the reader.  Two entries are in one class iff
+ * their D masks have the same membership at every node of run 0's post graph
+ * (so they also have the same missing events); an all-zero mask is a class like
+ * any other.  Classes are numbered by their smallest entry, ascending; that
+ * entry is the class's representative.  In NEMO_DIFF_REFERENCE and the label
+ * modes every entry shares one label source: one class of n_entries.           */
+typedef struct nemo_diff_class {
+  uint32_t rep;    /* representative: the class's smallest diff entry               */
+  uint32_t size;   /* member entries (duplicated failed_iters each count)           */
+  uint32_t nodes;  /* |D|: nodes of run 0's post graph in the class's mask          */
+} nemo_diff_class;
+/* Classifies the results of the last nemo_diffprov / _labels / _host_labels call
+ * on the device (the masks are not copied to the host for it).  NEMO_ERR_STATE
+ * when no corpus is loaded or no diffprov ran since the load; zero entries give
+ * zero classes.  Blocks until the classes are known.  A later nemo_diffprov*,
+ * nemo_load_corpus or nemo_rebuild invalidates the result (the fetches below
+ * then return NEMO_ERR_STATE until the next nemo_diff_classes);
+ * nemo_diffprov_symmetric leaves it valid, as it leaves the diff itself.       */
+int nemo_diff_classes(nemo_ctx *ctx);
+/* class_of[e] = class of entry e (may be NULL); classes[k] for every class k.
+ * classes == NULL queries *n_classes.                                          */
+int nemo_fetch_diff_classes(nemo_ctx *ctx, uint32_t *class_of /* [n_entries], may be NULL */,
+                            nemo_diff_class *classes, uint64_t cap, uint64_t *n_classes);
+/* Support of every node of run 0's post graph: out[v] = entries whose D holds v
+ * (duplicated entries each count); cap >= V0.                                  */
+int nemo_fetch_diff_support(nemo_ctx *ctx, uint32_t *out, uint64_t cap /* >= V0 */);
 
 /* ---- symmetric differential provenance ("bad - good") ----------------------
  * The half the reference's API names and never built: `symmetric` of

@@ -260,6 +260,11 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     if (c->cs.loaded) set_global_block(c);
     return NEMO_OK;
   }
+  if (!strcmp(name, "class_hash_bits")) {  // test knob: 0..128 low hash bits bucket the D masks (nemo_diff_classes)
+    if (value < -1 || value > 128) return fail(c, NEMO_ERR_INVALID, "class_hash_bits: 0..128, or -1");
+    c->opt.class_hash_bits = value < 0 ? 128 : (int)value;
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;
@@ -867,6 +872,7 @@ int nemo_rebuild(nemo_ctx *c) {
   if (rc) return rc;
   c->cs.marked = c->cs.simplified = c->cs.protos_done = c->cs.trig_done = false;
   c->cs.mark_pending = false;
+  c->cs.dc_done = false;
   return NEMO_OK;
 }
 

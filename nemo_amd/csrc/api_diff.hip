@@ -15,7 +15,9 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
   // (the diff kernels read no holds flags: a deferred mark stays fused with the simplification)
   HIPCHK(c, hipSetDevice(c->device));
   c->cs.n_entries = 0;
-  if (n_failed == 0 || c->cs.run0 < 0) return NEMO_OK;  // MATCH on run 0 finds nothing
+  c->cs.dc_done = false;  // the classes were those of the previous call's masks
+  c->cs.diff_done = n_failed == 0 || c->cs.run0 < 0;
+  if (c->cs.diff_done) return NEMO_OK;  // MATCH on run 0 finds nothing
   if (int re = ensure_event(c, &c->ev_up_dsrc)) return re;
   HIPCHK(c, hipEventSynchronize(c->ev_up_dsrc));  // the previous upload has landed (at once if there was none)
   if (int rg = c->h_dsrc.grow(c, 3 * n_failed)) return rg;
@@ -218,7 +220,9 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
   nemo::launch_to_host_multi(hc, s);
   HIPCHK(c, hipEventRecord(c->ev_diff, s));
   c->cs.aux_pending = true;
+  c->cs.diff_stream = s;
   c->cs.n_entries = (uint32_t)n_failed;
+  c->cs.diff_done = true;
   return NEMO_OK;
 }
 
@@ -358,6 +362,132 @@ int nemo_fetch_missing(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
       out[k].rule = r;
       k++;
     }
+  return NEMO_OK;
+}
+
+// ---- failure classes (DESIGN.md §Failure classes) ----
+// The D masks stay in HBM: k_dclass_hash reads the row of every distinct label source once (the
+// other entries share it through dmap), the host buckets the 128-bit hashes (dclass_host.h) and
+// k_dclass_cmp confirms every bucket member against its bucket's candidate, round by round.  The
+// kernels are queued behind the diff kernels on the stream those ran on (`aux` or the context's);
+// nothing here waits for ev_diff or reads h_mask.
+int nemo_diff_classes(nemo_ctx *c) {
+  DISPATCH(node_diff_classes(c));
+  if (!c) return NEMO_ERR_INVALID;
+  CorpusState &cs = c->cs;
+  if (!cs.loaded) return fail(c, NEMO_ERR_STATE, "nemo_diff_classes without a loaded corpus");
+  if (!cs.diff_done) return fail(c, NEMO_ERR_STATE, "nemo_diff_classes before nemo_diffprov");
+  cs.dc_done = false;
+  cs.dc_class_of.clear();
+  cs.dc_classes.clear();
+  cs.dc_hash.clear();
+  cs.dc_rounds = 0;
+  const uint32_t n = cs.n_entries, nu = cs.n_uniq;
+  const uint64_t V0 = cs.run0 >= 0 ? cs.node_off[2 * cs.run0 + 2] - cs.node_off[2 * cs.run0 + 1] : 0;
+  cs.dc_support.assign(V0, 0);
+  if (!n) {
+    cs.dc_done = true;
+    return NEMO_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_event(c, &c->ev_dclass))) return rc;
+  hipStream_t s = cs.diff_stream;  // behind the diff kernels, on whichever stream they ran
+  const uint32_t cap = (nu + 63u) & ~63u;
+  if (cap > cs.dc_cap || !cs.d_dcacc) {
+    for (void *q : {(void *)cs.d_dcacc, (void *)cs.d_dcin, (void *)cs.d_dcv}) dfree(c, q);
+    cs.d_dcacc = cs.d_dcin = nullptr;
+    cs.d_dcv = nullptr;
+    cs.dc_cap = 0;
+    if ((rc = dalloc(c, &cs.d_dcacc, 5 * (size_t)cap + V0))) return rc;
+    if ((rc = dalloc(c, &cs.d_dcin, 2 * (size_t)cap))) return rc;
+    if ((rc = dalloc(c, &cs.d_dcv, (size_t)cap))) return rc;
+    cs.dc_cap = cap;
+  }
+  if ((rc = c->h_dcin.grow(c, 2 * (uint64_t)cap))) return rc;
+  if ((rc = c->h_dcout.grow(c, 5 * (uint64_t)cap + V0))) return rc;
+  // every call ends with its last copy landed (below), so the staging buffers are free here
+  std::vector<uint32_t> first(nu, 0);  // source -> its first entry (urep; dmap numbers sources in that order)
+  for (uint32_t u = 0; u < nu; u++) c->h_dcin.p[u] = 0;
+  for (uint32_t e = n; e-- > 0;) {
+    c->h_dcin.p[cs.dmap[e]]++;
+    first[cs.dmap[e]] = e;
+  }
+  nemo::DclassArgs a{};
+  a.mask = cs.d_dmask;
+  a.V0 = V0;
+  a.row = cs.d_dsrc + 2 * (size_t)n;
+  a.weight = cs.d_dcin;
+  a.nu = nu;
+  a.rows_per_block = nemo::dclass_rows_per_block(V0, nu);
+  a.hash = reinterpret_cast<uint64_t *>(cs.d_dcacc);
+  a.pop = cs.d_dcacc + 4 * (size_t)cs.dc_cap;
+  a.support = cs.d_dcacc + 5 * (size_t)cs.dc_cap;
+  nemo::launch_to_host(cs.d_dcin, c->h_dcin.p, 4ull * nu, s);  // pinned -> device by a copy kernel
+  nemo::launch_zero(cs.d_dcacc, 4 * (5 * (uint64_t)cs.dc_cap + V0), s);
+  // algorithmic bytes: every distinct row once, 20 bytes per source and the support written
+  if ((rc = timed_on(c, s, "k_dclass", (double)nu * V0 + 24.0 * nu + 4.0 * V0, 0,
+                     [&] { nemo::launch_dclass_hash(a, s); })))
+    return rc;
+  uint32_t *h_hash = c->h_dcout.p, *h_pop = h_hash + 4 * (size_t)cap, *h_sup = h_pop + cap;
+  nemo::HostCopies hc;
+  hc.add(h_hash, a.hash, 16ull * nu);
+  hc.add(h_pop, a.pop, 4ull * nu);
+  hc.add(h_sup, a.support, 4ull * V0);
+  nemo::launch_to_host_multi(hc, s);
+  HIPCHK(c, hipEventRecord(c->ev_dclass, s));
+  HIPCHK(c, hipEventSynchronize(c->ev_dclass));
+  std::vector<dclass::Hash> hash(nu);
+  for (uint32_t u = 0; u < nu; u++) memcpy(&hash[u], h_hash + 4 * (size_t)u, 16);
+  std::vector<uint32_t> pop(h_pop, h_pop + nu);
+  cs.dc_support.assign(h_sup, h_sup + V0);
+  dclass::Refiner ref(hash.data(), nu, c->opt.class_hash_bits);
+  std::vector<uint32_t> pairs;
+  uint8_t *h_v = reinterpret_cast<uint8_t *>(c->h_dcout.p);
+  while (ref.next_round(pairs)) {
+    const uint32_t np = (uint32_t)(pairs.size() / 2);  // < nu
+    if (np) {
+      memcpy(c->h_dcin.p, pairs.data(), pairs.size() * 4);
+      nemo::launch_to_host(cs.d_dcin, c->h_dcin.p, 8ull * np, s);
+      // each verified row and its candidate once more
+      if ((rc = timed_on(c, s, "k_dclass", 2.0 * np * V0 + 9.0 * np, 0,
+                         [&] { nemo::launch_dclass_cmp(a, cs.d_dcin, np, cs.d_dcv, s); })))
+        return rc;
+      nemo::launch_to_host(h_v, cs.d_dcv, np, s);
+      HIPCHK(c, hipEventRecord(c->ev_dclass, s));
+      HIPCHK(c, hipEventSynchronize(c->ev_dclass));
+    }
+    ref.verdicts(h_v);
+  }
+  cs.dc_rounds = ref.rounds();
+  dclass::finish(ref.rep(), cs.dmap.data(), n, first.data(), pop.data(), cs.dc_class_of, cs.dc_classes);
+  for (uint32_t u = 0; u < nu; u++)
+    if (ref.rep()[u] == u) cs.dc_hash.push_back(hash[u]);
+  cs.dc_done = true;
+  return NEMO_OK;
+}
+
+int nemo_fetch_diff_classes(nemo_ctx *c, uint32_t *class_of, nemo_diff_class *classes, uint64_t cap, uint64_t *n_classes) {
+  DISPATCH(node_fetch_diff_classes(c, class_of, classes, cap, n_classes));
+  if (!c) return NEMO_ERR_INVALID;
+  if (!c->cs.dc_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_diff_classes before nemo_diff_classes (or after a later nemo_diffprov)");
+  const uint64_t k = c->cs.dc_classes.size();
+  if (n_classes) *n_classes = k;
+  if (class_of && !c->cs.dc_class_of.empty()) memcpy(class_of, c->cs.dc_class_of.data(), c->cs.dc_class_of.size() * 4);
+  if (!classes) return NEMO_OK;
+  if (cap < k) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (k) memcpy(classes, c->cs.dc_classes.data(), k * sizeof(nemo_diff_class));
+  return NEMO_OK;
+}
+
+int nemo_fetch_diff_support(nemo_ctx *c, uint32_t *out, uint64_t cap) {
+  DISPATCH(node_fetch_diff_support(c, out, cap));
+  if (!c) return NEMO_ERR_INVALID;
+  if (!c->cs.dc_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_diff_support before nemo_diff_classes (or after a later nemo_diffprov)");
+  const uint64_t V0 = c->cs.dc_support.size();
+  if (V0 && !out) return NEMO_ERR_INVALID;
+  if (cap < V0) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (V0) memcpy(out, c->cs.dc_support.data(), V0 * 4);
   return NEMO_OK;
 }
 

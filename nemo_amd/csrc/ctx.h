@@ -15,6 +15,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "dclass_host.h"
 #include "device.h"
 #include "internal.h"
 #include "node.h"
@@ -100,6 +101,7 @@ struct Options {
   uint32_t stage_blocks = 0;  // bulk staging: 0 = runtime copies, else k_to_host on this many blocks
   bool stage_sdma = false;    // runtime copies requested as NoCU (SDMA) copies (cleared if the runtime refuses)
   uint32_t stage_cus = 8;     // CUs of the copy stream (hipExtStreamCreateWithCUMask); 0 = unmasked
+  int class_hash_bits = 128;  // nemo_diff_classes buckets by the low k bits of the hash (test knob: forces collisions)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -171,6 +173,21 @@ struct CorpusState {
   bool dx_last = false;              // the last diffprov ran the multi-entry kernels
   uint32_t *d_hlab = nullptr;        // nemo_diffprov_host_labels' set [n, label...]
   uint64_t hlab_cap = 0;
+
+  // failure classes (k_dclass.hip): results of the last nemo_diff_classes, void after the next
+  // diffprov / rebuild; buffers grow only, per-source sizes in whole 64-source chunks
+  bool diff_done = false;            // a diffprov completed on the loaded corpus (n_entries may be 0)
+  bool dc_done = false;
+  hipStream_t diff_stream = nullptr;  // the stream the last diffprov's kernels went on (`aux` or the context's)
+  uint32_t dc_cap = 0;               // sources the buffers hold
+  uint32_t *d_dcacc = nullptr;       // [4 cap] hashes | [cap] |D| | [V0] support: zeroed, then summed into
+  uint32_t *d_dcin = nullptr;        // [2 cap] the sources' entry counts, then a round's (row, candidate) pairs
+  uint8_t *d_dcv = nullptr;          // [cap] a round's verdicts
+  std::vector<uint32_t> dc_class_of;
+  std::vector<nemo_diff_class> dc_classes;
+  std::vector<dclass::Hash> dc_hash;  // per class: its mask's hash (the node context merges shards by it)
+  std::vector<uint32_t> dc_support;  // [V0]
+  uint32_t dc_rounds = 0;            // comparison rounds the last call took
 
   // symmetric diff (k_sdiff.hip): all of it the call's own state, so that a symmetric call leaves
   // the results of a previous nemo_diffprov alone and the reverse; buffers grow only
@@ -258,9 +275,11 @@ struct nemo_ctx {
   // the hand-over kernels of nemo_stage_simplified on `aux`: behind everything `stream` has
   // queued so far, beside the triggers and pulls queued after
   hipEvent_t ev_stage = nullptr;
-  hipEvent_t *const events[18] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_dclass = nullptr;  // nemo_diff_classes' hashes / verdicts have reached pinned memory
+  hipEvent_t *const events[19] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
-                                  &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage};
+                                  &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
+                                  &ev_dclass};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -269,10 +288,13 @@ struct nemo_ctx {
   Pinned<uint32_t> h_hlab, h_dsrc, h_chht;
   Pinned<uint64_t> h_choff;
   PullHost h_pull;
-  void **const pinned[19] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  // nemo_diff_classes: h_dcin uploads (entry counts, pairs), h_dcout receives (hashes, |D|, support, verdicts)
+  Pinned<uint32_t> h_dcin, h_dcout;
+  void **const pinned[21] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
-                             h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot()};
+                             h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
+                             h_dcin.slot(),  h_dcout.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

@@ -138,6 +138,19 @@ struct SdiffArgs {
   uint32_t *n_rows;         // counter
 };
 
+// One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
+struct DclassArgs {
+  const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)
+  uint64_t V0;
+  const uint32_t *row;      // [nu] the entry whose row is source u's mask (DxArgs::urep)
+  const uint32_t *weight;   // [nu] entries of source u
+  uint32_t nu;
+  uint32_t rows_per_block;  // rows per k_dclass_hash workgroup (dclass_rows_per_block)
+  uint64_t *hash;           // [nu][2] membership hash, summed over column tiles (zeroed per call)
+  uint32_t *pop;            // [nu] |D| (zeroed per call)
+  uint32_t *support;        // [V0] entries whose D holds the node (zeroed per call)
+};
+
 struct PullArgs {
   uint32_t which;           // 0 raw, 1 simplified, 2 diff, 3 symmetric diff
   uint32_t g0;              // graph of which == 2
@@ -189,6 +202,10 @@ void launch_diff_expand(uint8_t *mask, const uint8_t *umask, const uint32_t *map
 // n_lds / n_glob: entries inside / past k_diff_lds's caps (host counts; an empty tier is not launched)
 void launch_sdiff(const DevCorpus &c, const SdiffArgs &a, uint32_t n_entries, uint32_t n_lds, uint32_t n_glob,
                   hipStream_t s);
+uint32_t dclass_rows_per_block(uint64_t V0, uint32_t nu);
+void launch_dclass_hash(const DclassArgs &a, hipStream_t s);
+// verdict[k] = 1 iff rows pairs[2k] and pairs[2k + 1] (sources) have the same membership at every node
+void launch_dclass_cmp(const DclassArgs &a, const uint32_t *pairs, uint32_t n_pairs, uint8_t *verdict, hipStream_t s);
 void launch_dx_prep(const DevCorpus &c, const DxPrep &p, uint32_t *tsum, hipStream_t s);
 void launch_dx(const DevCorpus &c, const DxArgs &a, hipStream_t s);
 uint32_t dx_max_row();       // the longest row of g0 the multi-entry diff takes

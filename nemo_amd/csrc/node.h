@@ -39,6 +39,9 @@ int node_fetch_diff_mask(nemo_ctx *c, uint32_t entry, uint8_t *out, uint64_t cap
 int node_fetch_diff_masks(nemo_ctx *c, uint8_t *out, uint64_t cap);
 int node_diff_masks_view(nemo_ctx *c, const uint8_t **masks, uint64_t *n_entries, uint64_t *v0);
 int node_fetch_missing(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n_out);
+int node_diff_classes(nemo_ctx *c);
+int node_fetch_diff_classes(nemo_ctx *c, uint32_t *class_of, nemo_diff_class *classes, uint64_t cap, uint64_t *n_classes);
+int node_fetch_diff_support(nemo_ctx *c, uint32_t *out, uint64_t cap);
 int node_triggers(nemo_ctx *c);
 int node_fetch_triggers(nemo_ctx *c, uint32_t *pre, uint64_t pre_cap, uint64_t *n_pre, uint32_t *post,
                         uint64_t post_cap, uint64_t *n_post, uint32_t *async_rules, uint64_t async_cap,

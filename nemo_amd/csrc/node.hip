@@ -135,6 +135,11 @@ struct Node {
   uint32_t n_entries = 0;
   std::vector<uint32_t> entry_shard, entry_local;
   int pull_which = -1;
+  // failure classes of the last node_diff_classes, in global entry numbering
+  bool dc_done = false;
+  int class_bits = 128;  // option class_hash_bits, for the merge of the shards' classes
+  std::vector<uint32_t> class_of, support;
+  std::vector<nemo_diff_class> classes;
   // assembled host views
   std::vector<uint8_t> state, masks;
   std::vector<uint64_t> choff;
@@ -276,6 +281,7 @@ int node_set_stream(nemo_ctx *c, void *stream) {
 }
 int node_set_option(nemo_ctx *c, const char *name, int64_t value) {
   for (auto &s : N(c)->sh) SCHK(c, s, nemo_set_option(s.ctx, name, value));
+  if (name && !strcmp(name, "class_hash_bits")) N(c)->class_bits = value < 0 ? 128 : (int)value;
   return NEMO_OK;
 }
 int node_set_timing(nemo_ctx *c, int enable) {
@@ -399,6 +405,7 @@ int node_load_corpus(nemo_ctx *c, const nemo_corpus *in) {
   for (uint32_t p = 0; p < P; p++) SCHK(c, n->sh[p], rcs[p]);
   n->n_entries = 0;
   n->pull_which = -1;
+  n->dc_done = false;
   n->loaded = true;
   return NEMO_OK;
 }
@@ -409,6 +416,7 @@ int node_load_corpus(nemo_ctx *c, const nemo_corpus *in) {
 int node_rebuild(nemo_ctx *c) {
   Node *n = N(c);
   NEED_LOADED(c, n);
+  n->dc_done = false;
   return fanout(c, n, [](Shard &s, size_t) { return nemo_rebuild(s.ctx); });
 }
 int node_mark_holds(nemo_ctx *c) {
@@ -568,6 +576,7 @@ static int node_diff(nemo_ctx *c, const uint32_t *failed, size_t nf, int mode, c
   NEED_LOADED(c, n);
   if (!failed && nf) return fail(c, NEMO_ERR_INVALID, "null failed list");
   if (mode != NEMO_DIFF_REFERENCE && mode != NEMO_DIFF_PER_RUN) return fail(c, NEMO_ERR_INVALID, "unknown diff mode %d", mode);
+  n->dc_done = false;
   const size_t P = n->sh.size();
   std::vector<std::vector<uint32_t>> lists(P);
   n->entry_shard.assign(nf, 0);
@@ -623,6 +632,7 @@ int node_diffprov_host_labels(nemo_ctx *c, const uint32_t *failed, size_t nf, co
   Node *n = N(c);
   NEED_LOADED(c, n);
   // route the entries as node_diff does, every shard with the same host label set
+  n->dc_done = false;
   const size_t P = n->sh.size();
   std::vector<std::vector<uint32_t>> lists(P);
   n->entry_shard.assign(nf, 0);
@@ -714,6 +724,91 @@ int node_fetch_missing(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
   if (!out) return NEMO_OK;
   if (cap < all.size()) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(nemo_missing));
+  return NEMO_OK;
+}
+
+// ---- failure classes: every shard classifies its entries, the node merges the classes ----
+// Run 0 is replicated, so a mask's hash and V0 are the same on every shard: the shards' classes are
+// bucketed by hash like the sources of one device (dclass_host.h), in order of their global
+// representative, and equality is confirmed on the representatives' rows, which every shard's
+// nemo_diffprov has already copied to its pinned masks.
+int node_diff_classes(nemo_ctx *c) {
+  Node *n = N(c);
+  NEED_LOADED(c, n);
+  n->dc_done = false;
+  if (int rc = fanout(c, n, [](Shard &s, size_t) { return nemo_diff_classes(s.ctx); })) return rc;
+  const size_t P = n->sh.size();
+  const uint64_t V0 = v0_of(n);
+  struct Item {
+    uint32_t rep, shard, cls, nodes;
+    dclass::Hash h;
+    const uint8_t *row;
+  };
+  std::vector<Item> items;
+  n->support.assign(V0, 0);
+  for (size_t p = 0; p < P; p++) {
+    Shard &s = n->sh[p];
+    const CorpusState &cs = s.ctx->cs;
+    if (!n->n_entries || cs.dc_classes.empty()) continue;
+    const uint8_t *m = nullptr;
+    SCHK(c, s, nemo_diff_masks_view(s.ctx, &m, nullptr, nullptr));
+    for (size_t k = 0; k < cs.dc_classes.size(); k++) {
+      const nemo_diff_class &q = cs.dc_classes[k];
+      items.push_back({s.entries[q.rep], (uint32_t)p, (uint32_t)k, q.nodes, cs.dc_hash[k], m + (size_t)q.rep * V0});
+    }
+    for (uint64_t v = 0; v < V0 && v < cs.dc_support.size(); v++) n->support[v] += cs.dc_support[v];
+  }
+  std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.rep < b.rep; });
+  const uint32_t ni = (uint32_t)items.size();
+  std::vector<dclass::Hash> hash(ni);
+  std::vector<uint32_t> first(ni), nodes(ni);
+  std::vector<std::vector<uint32_t>> item_at(P);  // shard, local class -> item
+  for (size_t p = 0; p < P; p++) item_at[p].assign(n->sh[p].ctx->cs.dc_classes.size(), 0);
+  for (uint32_t i = 0; i < ni; i++) {
+    hash[i] = items[i].h;
+    first[i] = items[i].rep;
+    nodes[i] = items[i].nodes;
+    item_at[items[i].shard][items[i].cls] = i;
+  }
+  dclass::Refiner ref(hash.data(), ni, n->class_bits);
+  std::vector<uint32_t> pairs;
+  std::vector<uint8_t> verdict;
+  while (ref.next_round(pairs)) {
+    verdict.assign(pairs.size() / 2 + 1, 0);
+    for (size_t k = 0; k < pairs.size() / 2; k++) {
+      const uint8_t *a = items[pairs[2 * k]].row, *b = items[pairs[2 * k + 1]].row;
+      uint64_t v = 0;
+      while (v < V0 && (a[v] != 0) == (b[v] != 0)) v++;
+      verdict[k] = v == V0;
+    }
+    ref.verdicts(verdict.data());
+  }
+  std::vector<uint32_t> item_of(n->n_entries, 0);
+  for (uint32_t e = 0; e < n->n_entries; e++) {
+    const uint32_t p = n->entry_shard[e];
+    item_of[e] = item_at[p][n->sh[p].ctx->cs.dc_class_of[n->entry_local[e]]];
+  }
+  dclass::finish(ref.rep(), item_of.data(), n->n_entries, first.data(), nodes.data(), n->class_of, n->classes);
+  n->dc_done = true;
+  return NEMO_OK;
+}
+int node_fetch_diff_classes(nemo_ctx *c, uint32_t *class_of, nemo_diff_class *classes, uint64_t cap, uint64_t *n_classes) {
+  Node *n = N(c);
+  if (!n->dc_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_diff_classes before nemo_diff_classes (or after a later nemo_diffprov)");
+  const uint64_t k = n->classes.size();
+  if (n_classes) *n_classes = k;
+  if (class_of && !n->class_of.empty()) memcpy(class_of, n->class_of.data(), n->class_of.size() * 4);
+  if (!classes) return NEMO_OK;
+  if (cap < k) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (k) memcpy(classes, n->classes.data(), k * sizeof(nemo_diff_class));
+  return NEMO_OK;
+}
+int node_fetch_diff_support(nemo_ctx *c, uint32_t *out, uint64_t cap) {
+  Node *n = N(c);
+  if (!n->dc_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_diff_support before nemo_diff_classes (or after a later nemo_diffprov)");
+  if (!n->support.empty() && !out) return fail(c, NEMO_ERR_INVALID, "null output");
+  if (cap < n->support.size()) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (!n->support.empty()) memcpy(out, n->support.data(), n->support.size() * 4);
   return NEMO_OK;
 }
 

@@ -94,6 +94,9 @@ def lib():
             "nemo_fetch_missing": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_diff_masks": ([vp, vp, u64], i32),
             "nemo_diff_masks_view": ([vp, vp, vp, vp], i32),
+            "nemo_diff_classes": ([vp], i32),
+            "nemo_fetch_diff_classes": ([vp, vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_diff_support": ([vp, vp, u64], i32),
             "nemo_diffprov_symmetric": ([vp, vp, sz], i32),
             "nemo_fetch_sdiff_masks": ([vp, vp, vp, u64, P(u64)], i32),
             "nemo_fetch_surplus": ([vp, vp, u64, P(u64)], i32),
@@ -388,6 +391,31 @@ class Engine:
         buf = (CMissing * max(n.value, 1))()
         self._chk(self.L.nemo_fetch_missing(self.h, buf, n.value, ctypes.byref(n)))
         return np.frombuffer(buf, dtype=np.uint32).reshape(-1, 2)[:n.value].copy()
+
+    def diff_classes(self):
+        """nemo_diff_classes + nemo_fetch_diff_classes: the entries of the last diffprov grouped by
+        identical D mask.  Returns (class_of[n_entries], classes[n_classes, 3]) as uint32 arrays;
+        a classes row is (representative entry, member entries, |D|), classes are numbered by
+        their smallest entry."""
+        self._chk(self.L.nemo_diff_classes(self.h))
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_diff_classes(self.h, None, None, 0, ctypes.byref(n)))
+        classes = np.zeros((max(n.value, 1), 3), np.uint32)
+        self._chk(self.L.nemo_fetch_diff_classes(self.h, None, classes.ctypes.data, n.value, ctypes.byref(n)))
+        classes = classes[:n.value]
+        class_of = np.zeros(max(int(classes[:, 1].sum()), 1), np.uint32)  # the sizes add up to the entries
+        self._chk(self.L.nemo_fetch_diff_classes(self.h, class_of.ctypes.data, None, 0, ctypes.byref(n)))
+        return class_of[:int(classes[:, 1].sum())], classes
+
+    def diff_support(self) -> np.ndarray:
+        """nemo_fetch_diff_support (after diff_classes): per node of run 0's post graph, the entries
+        whose D holds it."""
+        c = self.corpus
+        has0 = 0 in set(int(x) for x in c.iteration)
+        V0 = c.graph_size(2 * c.run_index(0) + 1) if has0 else 0
+        out = np.zeros(max(V0, 1), np.uint32)
+        self._chk(self.L.nemo_fetch_diff_support(self.h, out.ctypes.data, V0))
+        return out[:V0]
 
     def sdiff_masks(self) -> List[np.ndarray]:
         """S mask of every symmetric-diff entry: one uint8 array per entry, over the nodes of the

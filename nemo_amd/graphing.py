@@ -162,6 +162,18 @@ def time_holds(run: dict, cond: str) -> Dict[str, bool]:
     return {row[-1]: True for row in rows}
 
 
+def failure_class_order(failedRuns: Sequence[int], class_of: Sequence[int],
+                        classes: Sequence[Sequence[int]]) -> List[Tuple[int, int, List[int]]]:
+    """Orders the classes of Engine.diff_classes for a report: largest class first, ties by
+    representative entry.  Returns (class, representative's iteration, member iterations in entry
+    order) per class; duplicated failed runs appear once per entry."""
+    members: List[List[int]] = [[] for _ in classes]
+    for e, k in enumerate(class_of):
+        members[int(k)].append(int(failedRuns[e]))
+    order = sorted(range(len(classes)), key=lambda k: (-int(classes[k][1]), int(classes[k][0])))
+    return [(k, int(failedRuns[int(classes[k][0])]), members[k]) for k in order]
+
+
 def _rewrite(id_: str, old: int, new: int) -> str:
     """The `id`:"run_<old> -> run_<new> prefix rewrite of the exports
     (preprocessing.go:33-45, differential-provenance.go:46-55)."""
@@ -358,6 +370,24 @@ class Neo4J:
         if symmetric:
             faileds = self._surplus(failedRuns)
         return diffs, faileds, missing
+
+    def FailureClasses(self, failedRuns: Sequence[int], successPostProv: Optional[DotGraph] = None) -> List[dict]:
+        """The distinct failure modes among failedRuns (no reference counterpart; summarises
+        CreateNaiveDiffProv): the runs are grouped by identical differential provenance on the device
+        (nemo_diff_classes).  One record per class, largest class first, ties by representative:
+        {"Representative": iteration, "Members": iterations, "Nodes": |D|, "Missing": the
+        representative's missing events, "Diff": its diff DOT}, the last two as CreateNaiveDiffProv
+        returns them for the representative, computed once per class.  successPostProv defaults to
+        the good run's raw post provenance."""
+        if successPostProv is None:
+            successPostProv = create_dot(self._edges(None, self._g(0, "post")), "post")
+        self.eng.diffprov(failedRuns, self.diff_mode)
+        class_of, classes = self.eng.diff_classes()
+        order = failure_class_order(failedRuns, class_of.tolist(), classes.tolist())
+        # (in the reference mode failedRuns[0] labels every entry and is the one representative)
+        diffs, _, missing = self.CreateNaiveDiffProv(False, [rep for _, rep, _ in order], successPostProv)
+        return [{"Representative": rep, "Members": mem, "Nodes": int(classes[k][2]), "Missing": missing[i],
+                 "Diff": diffs[i]} for i, (k, rep, mem) in enumerate(order)]
 
     def _surplus(self, failedRuns: Sequence[int]) -> List[DotGraph]:
         """The symmetric half: S masks, surplus events (kept in self.SurplusEvents) and the
