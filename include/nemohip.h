@@ -58,7 +58,9 @@ extern "C" {
 #define NEMO_TYPE_NEXT    1u  /* "next"  (preprocessing.go:71, corrections.go:213) */
 #define NEMO_TYPE_ASYNC   2u  /* "async" (extensions.go:64, diagrams.go:53)    */
 #define NEMO_TABLE_MASK   0x00FFFFFFu
-#define NEMO_MAX_TABLES   16384u /* table-id universe supported by this build   */
+#define NEMO_MAX_TABLES   16384u /* table-id universe supported by this build: 512 words of per-run
+                                    bitset; exercised up to the limit on every tier by
+                                    tests/test_gpu_tables.py and tests/test_tables_host.py */
 
 #define NEMO_WORD(is_rule, type, table) \
   (((is_rule) ? NEMO_NODE_RULE : 0u) | ((uint32_t)(type) << NEMO_TYPE_SHIFT) | ((uint32_t)(table) & NEMO_TABLE_MASK))
