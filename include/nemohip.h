@@ -195,7 +195,21 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       their 128-bit hash, k in 0..128 (default 128); every
  *                       bucket is verified by exact row comparisons, so fewer bits
  *                       only force collisions and more comparison rounds (test
- *                       knob; at 0 every mask collides with every other) */
+ *                       knob; at 0 every mask collides with every other)
+ *   "graph_dedup"       1 (default): nemo_load_corpus groups the graphs of identical
+ *                       content (sizes, pre / post, node words, labels, ID ranks,
+ *                       edges in stored order); k_build, k_marksimp and the first
+ *                       chain tier then run on one graph per class and a streaming
+ *                       copy fills the others' slices, so every array holds what
+ *                       it held without the option.  Graphs of 8192 nodes or more
+ *                       and the deep graphs are kept apart.  0: every graph runs
+ *                       (no classes are made by a load under 0; set it before the
+ *                       load).  Not applied under "load_async" 1 or to a corpus
+ *                       uploaded in parts
+ *   "dedup_hash_bits"   that grouping buckets by the low k bits of a 128-bit
+ *                       content hash, k in 0..128 (default 128; takes effect at the
+ *                       next load); every bucket is confirmed by exact comparisons
+ *                       (test knob, as "class_hash_bits") */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);

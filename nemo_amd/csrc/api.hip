@@ -9,6 +9,19 @@ static void set_lds_tier(nemo_ctx *c);
 static void set_global_block(nemo_ctx *c);
 static void set_build_tier(nemo_ctx *c);
 
+// the kernels' graph list: the representatives while the option is on and the load found duplicates
+static void set_graph_dedup(nemo_ctx *c) {
+  const bool on = c->opt.graph_dedup && c->cs.gd_npairs != 0;
+  c->cs.dc.dd_list = on ? c->cs.d_gd_list : nullptr;
+  c->cs.dc.dd_n = on ? c->cs.gd_nlist : 0;
+}
+// a replicate pass behind `phase`'s kernel (k_gdedup.hip); nothing without duplicates
+static int replicate(nemo_ctx *c, int phase) {
+  if (!c->cs.dc.dd_list) return NEMO_OK;
+  return timed(c, "k_replicate", c->cs.gd_bytes[phase], 0,
+               [&] { nemo::launch_replicate(c->cs.dc, c->cs.d_gd_pairs, c->cs.gd_npairs, phase, c->stream); });
+}
+
 static void tiers_reset(nemo_ctx *c) {
   c->cs.tiers_ok = c->cs.tiers_pending = false;
   c->cs.tiers_run = 0;
@@ -265,6 +278,16 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.class_hash_bits = value < 0 ? 128 : (int)value;
     return NEMO_OK;
   }
+  if (!strcmp(name, "graph_dedup")) {  // 0: every graph runs its own workgroup, nothing is replicated
+    c->opt.graph_dedup = value != 0;
+    set_graph_dedup(c);
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "dedup_hash_bits")) {  // test knob: 0..128 low hash bits bucket the graphs; takes effect at the next load
+    if (value < -1 || value > 128) return fail(c, NEMO_ERR_INVALID, "dedup_hash_bits: 0..128, or -1");
+    c->opt.dedup_hash_bits = value < 0 ? 128 : (int)value;
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;
@@ -472,6 +495,7 @@ static int device_load(nemo_ctx *c, const LoadParts *lp = nullptr) {
   if ((rc = timed(c, "k_build", 16 * Eb + (c->cs.dc.ms_fuse ? 21 : 20) * Vb + 4 * Ep + 4 * Vp, 2 * Eb,
                   [&] { nemo::launch_build(c->cs.dc, c->stream); })))
     return rc;
+  if ((rc = replicate(c, GD_BUILD))) return rc;  // before k_load_sel reads the duplicates' redo flags
   c->cs.ms_fused = c->cs.dc.ms_fuse != 0;
   // graphs past k_build: k_csr (one workgroup per graph) below NEMO_CSR_BIG nodes, k_csrb_* above
   const double Eg = std::max(0.0, E - c->cs.bigE), Vg = std::max(0.0, V - c->cs.bigV);
@@ -819,6 +843,75 @@ int Load::load_trigger_caps() {
   return rc;
 }
 
+// The load's duplicate classes (DESIGN.md §3 "Duplicate graphs"): a content hash per graph on the
+// device, buckets and comparison rounds on the host (gdedup_host.h), every bucket confirmed by exact
+// comparisons on the device, so the classes never rest on the hash.  Behind the uploads on `stream`,
+// before the first k_build.  Graphs of NEMO_CSR_BIG nodes or more and the deep graphs
+// (chains_glob_min_v) stay their own representatives: their kernels are not per graph.
+static int load_graph_classes(nemo_ctx *c, bool dbg) {
+  CorpusState &s = c->cs;
+  const uint32_t G = s.G;
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t *d_hash = nullptr;
+  uint8_t *d_verdict = nullptr;
+  int rc;
+  if ((rc = dalloc(c, &d_hash, 2 * (size_t)G)) || (rc = dalloc(c, &s.d_gd_list, G)) ||
+      (rc = dalloc(c, &s.d_gd_pairs, 2 * (size_t)G)) || (rc = dalloc(c, &d_verdict, G)))
+    return rc;
+  hipStream_t st = c->stream;
+  nemo::launch_gd_hash(s.dc, d_hash, st);
+  std::vector<dclass::Hash> h(G);
+  HIPCHK(c, hipMemcpyAsync(h.data(), d_hash, 16 * (size_t)G, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  dclass::Refiner ref(h.data(), G, c->opt.dedup_hash_bits);
+  std::vector<uint32_t> pairs;
+  std::vector<uint8_t> verdict;
+  while (ref.next_round(pairs)) {
+    const uint32_t n = (uint32_t)(pairs.size() / 2);  // < G: every pair has its own first graph
+    verdict.assign(n, 0);
+    if (n) {
+      HIPCHK(c, hipMemcpyAsync(s.d_gd_pairs, pairs.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
+      nemo::launch_gd_cmp(s.dc, s.d_gd_pairs, n, d_verdict, st);
+      HIPCHK(c, hipMemcpyAsync(verdict.data(), d_verdict, n, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+    }
+    ref.verdicts(verdict.data());
+  }
+  std::vector<uint8_t> eligible(G);
+  for (uint32_t g = 0; g < G; g++) {
+    const uint64_t v = s.node_off[g + 1] - s.node_off[g];
+    eligible[g] = v < NEMO_CSR_BIG && v < c->opt.glob_min_v;
+  }
+  gdedup::Plan p = gdedup::plan(ref.rep(), eligible, s.node_off.data());
+  s.gd_nlist = (uint32_t)p.list.size();
+  s.gd_npairs = (uint32_t)(p.pairs.size() / 2);
+  s.gd_classes = p.classes;
+  s.gd_rounds = ref.rounds();
+  if (s.gd_npairs) {
+    HIPCHK(c, hipMemcpyAsync(s.d_gd_list, p.list.data(), 4 * p.list.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s.d_gd_pairs, p.pairs.data(), 4 * p.pairs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));  // the plan goes out of scope
+    double dv = 0, de = 0, dvp = 0, dep = 0;
+    for (uint32_t k = 0; k < s.gd_npairs; k++) {
+      const uint32_t g = p.pairs[2 * k];
+      const double v = (double)(s.node_off[g + 1] - s.node_off[g]), e = (double)(s.edge_off[g + 1] - s.edge_off[g]);
+      dv += v, de += e;
+      if (g & 1) dvp += v, dep += e;
+    }
+    s.gd_bytes[GD_BUILD] = 2 * (4 * (5 * dv + 2 * de) + 4 * (dvp + dep));  // read and written
+    s.gd_bytes[GD_MARKSIMP] = 2 * dv;
+    s.gd_bytes[GD_CHAINS] = 0;
+  }
+  s.gd_rep = std::move(p.rep);
+  set_graph_dedup(c);
+  if (dbg)
+    fprintf(stderr, "nemo_load_corpus: duplicate graphs: %u graphs, %u classes + %u kept apart, %u duplicates, %.1f %% of "
+            "the nodes in duplicates, %u rounds, %.1f ms\n",
+            G, s.gd_classes, s.gd_nlist - s.gd_classes, s.gd_npairs, s.V ? 100.0 * (double)p.dup_nodes / (double)s.V : 0.0,
+            s.gd_rounds, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return NEMO_OK;
+}
+
 int nemo_load_corpus(nemo_ctx *c, const nemo_corpus *in) {
   DISPATCH(node_load_corpus(c, in));
   if (!c || !in) return NEMO_ERR_INVALID;
@@ -847,6 +940,10 @@ int nemo_load_corpus(nemo_ctx *c, const nemo_corpus *in) {
   if (dbg)
     fprintf(stderr, "nemo_load_corpus: host part done %.1f ms; %u dalloc calls, size hash %016llx\n", ms_since(),
             (unsigned)c->dalloc_n, (unsigned long long)c->dalloc_hash);
+  // not with load_async (the pass waits for its hashes) nor with an upload in parts (the edges
+  // arrive inside device_load; those corpora are big graphs, which are kept apart anyway)
+  if (c->opt.graph_dedup && !c->opt.load_async && L.lp.part.empty() && L.G > 1 && (rc = load_graph_classes(c, dbg)))
+    return rc;
   if ((rc = device_load(c, L.lp.part.empty() ? nullptr : &L.lp))) return rc;
   if (c->opt.load_async) {
     c->cs.load_check_pending = true;  // the checks wait on `stream` at the next call that reads the graphs
@@ -911,6 +1008,7 @@ int nemo_simplify(nemo_ctx *c) {
         (rc = timed(c, "k_marksimp", 8 * E + 5 * V, 5 * E,
                     [&] { nemo::launch_marksimp(c->cs.dc, c->stream, skip_built); })))
       return rc;
+    if ((rc = replicate(c, GD_MARKSIMP))) return rc;  // also what k_build's tail wrote (ms_fused)
     rc = timed(c, "k_simplify", 8 * Eg + 14 * Vg, 2 * Eg,
                [&] { nemo::launch_simplify(c->cs.dc, true, c->stream, c->cs.ms_rest != 0); });
     if (rc) return rc;
@@ -928,7 +1026,7 @@ int nemo_simplify(nemo_ctx *c) {
   // reads: flags 1 + Kahn level 4 + node word 4 (+ ID rank 4) per node, the edge list 8 per edge
   const bool chain_tiers = !tier_empty(c, 1);
   rc = timed(c, "k_chains", (c->cs.has_rank ? 13 : 9) * V + 8 * E, 0,
-             [&] { nemo::launch_chains(c->cs.dc, c->stream, chain_tiers); });
+             [&] { nemo::launch_chains(c->cs.dc, c->stream, chain_tiers, c->cs.d_gd_pairs, c->cs.gd_npairs); });
   if (rc) return rc;
   if (chain_tiers) c->cs.tiers_run |= 2u;
   if ((rc = ensure_event(c, &c->ev_simp))) return rc;

@@ -17,6 +17,7 @@
 
 #include "dclass_host.h"
 #include "device.h"
+#include "gdedup_host.h"
 #include "internal.h"
 #include "node.h"
 
@@ -102,6 +103,8 @@ struct Options {
   bool stage_sdma = false;    // runtime copies requested as NoCU (SDMA) copies (cleared if the runtime refuses)
   uint32_t stage_cus = 8;     // CUs of the copy stream (hipExtStreamCreateWithCUMask); 0 = unmasked
   int class_hash_bits = 128;  // nemo_diff_classes buckets by the low k bits of the hash (test knob: forces collisions)
+  bool graph_dedup = true;    // option graph_dedup: the per-graph kernels run on one graph per distinct content
+  int dedup_hash_bits = 128;  // the load's duplicate classes bucket by the low k bits of the hash (test knob)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -142,6 +145,15 @@ struct CorpusState {
   // ~10 empty launches cost ~6 us on the analysis stream).  Reset by a load and by any option.
   bool tiers_pending = false, tiers_ok = false;
   uint32_t tiers[3] = {0, 0, 0}, tiers_run = 0;
+
+  // Duplicate graphs (k_gdedup.hip, gdedup_host.h): classes of identical content, found once per
+  // load (the inputs do not change until the next load; nemo_rebuild keeps them).  dc.dd_list is
+  // d_gd_list while the option graph_dedup is on and the load found a duplicate, else null.
+  std::vector<uint32_t> gd_rep;      // [G] graph -> its representative (empty: the load made no classes)
+  uint32_t gd_nlist = 0, gd_npairs = 0, gd_classes = 0, gd_rounds = 0;
+  uint32_t *d_gd_list = nullptr;     // [gd_nlist] the representatives
+  uint32_t *d_gd_pairs = nullptr;    // [2 gd_npairs] (dup, rep) sorted by rep
+  double gd_bytes[3] = {0, 0, 0};    // what a replicate pass writes per phase at most (timing table)
 
   // diff
   uint32_t n_entries = 0, diff_cap = 0, legacy_cap = 0;

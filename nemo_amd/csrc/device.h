@@ -248,6 +248,12 @@ struct DevCorpus {
   uint32_t *proto_bits, *graph_tables;   // [n_runs*words]
   uint8_t *gate;                         // [n_runs]
   unsigned long long *stamps;            // diagnostic builds only: [16*G] phase stamps
+  // duplicate graphs (k_gdedup.hip): the representatives, ascending; null = every graph runs (no
+  // duplicates, or option graph_dedup 0).  k_build, k_marksimp and k_chains take graph dd_list[blockIdx.x]
+  const uint32_t *dd_list;
+  uint32_t dd_n;
+  __device__ __forceinline__ uint32_t graph_of_block() const { return dd_list ? dd_list[blockIdx.x] : blockIdx.x; }
+  __host__ uint32_t graph_blocks() const { return dd_list ? dd_n : G; }
 
   __device__ __forceinline__ GraphView view(uint32_t g) const {
     GraphView v;

@@ -188,7 +188,17 @@ void launch_csr_big(const DevCorpus &c, uint32_t chunks, hipStream_t s);
 void launch_mark(const DevCorpus &c, bool skip_tier, hipStream_t s, bool per_graph = true);
 void launch_simplify(const DevCorpus &c, bool skip_tier, hipStream_t s, bool per_graph = true);
 void launch_marksimp(const DevCorpus &c, hipStream_t s, bool skip_built);
-void launch_chains(const DevCorpus &c, hipStream_t s, bool tiers = true);
+// dd_pairs: the duplicate graphs' (dup, rep) pairs, replicated behind the first tier when c.dd_list is set
+void launch_chains(const DevCorpus &c, hipStream_t s, bool tiers = true, const uint32_t *dd_pairs = nullptr,
+                   uint32_t dd_npairs = 0);
+// duplicate graphs (k_gdedup.hip): content hashes [2 G] and exact comparisons at load; k_replicate
+// copies what `phase` wrote for each pair's representative to its duplicate
+#define GD_BUILD 0
+#define GD_MARKSIMP 1
+#define GD_CHAINS 2
+void launch_gd_hash(const DevCorpus &c, uint64_t *hash, hipStream_t s);
+void launch_gd_cmp(const DevCorpus &c, const uint32_t *pairs, uint32_t n_pairs, uint8_t *verdict, hipStream_t s);
+void launch_replicate(const DevCorpus &c, const uint32_t *pairs, uint32_t n_pairs, int phase, hipStream_t s);
 void launch_chains_glob(const DevCorpus &c, hipStream_t s);
 uint64_t glob_words(uint64_t V, uint64_t E);  // k_chains_glob scratch of one graph (u32)
 uint32_t glob_team_words();                   // k_glob_prep's team scratch (u32)

@@ -765,7 +765,7 @@ __global__ __launch_bounds__(PROTO_BLOCK) void k_proto_lds(DevCorpus c) {
 __global__ __launch_bounds__(MS_BLOCK) void k_marksimp(DevCorpus c, int skip_built) {
   extern __shared__ __align__(16) uint8_t dyn[];
   __shared__ uint32_t s_misc[3];
-  const uint32_t g = blockIdx.x;
+  const uint32_t g = c.graph_of_block();
   if (c.err[g]) return;
   const GraphView gv = c.view(g);
   if (!tier_fits(c.t_ms, gv.V, gv.E, gv.nlev)) return;
@@ -862,7 +862,7 @@ void launch_marksimp(const DevCorpus &c, hipStream_t s, bool skip_built) {
   if (!c.t_ms.bytes) return;
   const uint32_t b = c.t_ms.bytes;
   hipFuncSetAttribute((const void *)k_marksimp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  hipLaunchKernelGGL(k_marksimp, dim3(c.G), dim3(MS_BLOCK), b, s, c, skip_built ? 1 : 0);
+  hipLaunchKernelGGL(k_marksimp, dim3(c.graph_blocks()), dim3(MS_BLOCK), b, s, c, skip_built ? 1 : 0);
 }
 void launch_proto(const DevCorpus &c, hipStream_t s, bool tiers) {
   if (c.lds_bytes) {

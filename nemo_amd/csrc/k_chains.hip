@@ -1225,7 +1225,7 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_chains_sel(DevCorpus c) {
 #define CH_WPE_ATTR __attribute__((amdgpu_waves_per_eu(CH_WPE)))
 template <int HCAP, int UCAP>
 __global__ __launch_bounds__(NEMO_BLOCK) CH_WPE_ATTR void k_chains(DevCorpus c) {
-  chains_graph<HCAP, UCAP>(c, blockIdx.x);
+  chains_graph<HCAP, UCAP>(c, c.graph_of_block());
 }
 
 // The list gets a kernel of its own, so the first tier's stays at 119 VGPRs
@@ -1241,9 +1241,12 @@ __global__ __launch_bounds__(NEMO_BLOCK) __attribute__((amdgpu_waves_per_eu(3)))
 }
 
 #define CHAINS_GRID 1024u
-void launch_chains(const DevCorpus &c, hipStream_t s, bool tiers) {
+void launch_chains(const DevCorpus &c, hipStream_t s, bool tiers, const uint32_t *dd_pairs, uint32_t dd_npairs) {
   if (!c.G) return;
-  hipLaunchKernelGGL((k_chains<CH_HCAP, 120>), dim3(c.G), dim3(NEMO_BLOCK), 0, s, c);
+  hipLaunchKernelGGL((k_chains<CH_HCAP, 120>), dim3(c.graph_blocks()), dim3(NEMO_BLOCK), 0, s, c);
+  // the duplicates' chain records and counts before the second tier is listed: what the first tier
+  // handed back (nch = NEMO_NONE) is listed and redone per graph, duplicates included
+  if (c.dd_list) launch_replicate(c, dd_pairs, dd_npairs, GD_CHAINS, s);
   if (!tiers) {  // the host knows the first tier hands nothing back (api.hip tiers_known)
     launch_chains_glob(c, s);
     return;

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(BLD_OCC(B))))
   __shared__ uint32_t s_bad, s_created, s_tail, s_cnt[3];
   __shared__ uint32_t s_sink[64];  // per-lane no-op atomic targets (one bank each: no same-address serialisation)
   __shared__ uint32_t s_ms[3];
-  const uint32_t g = blockIdx.x, tid = threadIdx.x;
+  const uint32_t g = c.graph_of_block(), tid = threadIdx.x;
   const uint64_t n0 = c.node_off[g], e0 = c.edge_off[g];
   const uint32_t V = (uint32_t)(c.node_off[g + 1] - n0), E = (uint32_t)(c.edge_off[g + 1] - e0);
   if (!build_fits(c, V, E)) return;
@@ -1246,7 +1246,7 @@ void launch_build(const DevCorpus &c, hipStream_t s) {
 #endif
   hipFuncSetAttribute((const void *)k_build<BLD_BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)(c.bld_bytes + BLD_PAD));
-  hipLaunchKernelGGL(k_build<BLD_BLOCK>, dim3(c.G), dim3(BLD_BLOCK), c.bld_bytes + BLD_PAD, s, c);
+  hipLaunchKernelGGL(k_build<BLD_BLOCK>, dim3(c.graph_blocks()), dim3(BLD_BLOCK), c.bld_bytes + BLD_PAD, s, c);
 }
 void launch_load(const DevCorpus &c, hipStream_t s) {
   if (!c.G) return;
