@@ -571,6 +571,83 @@ func (n *Neo4J) CreateNaiveDiffProv(symmetric bool, failedRuns []uint, successPo
 	return diffDots, failedDots, missing, nil
 }
 
+// PairDiff is the differential provenance of one pair of runs: what the base
+// run's consequent provenance has that the other run lacks.
+type PairDiff struct {
+	Base, Other uint          // iterations
+	Mask        []uint8       // one byte per node of the base run's post graph: 1 = in the diff
+	Edges       []graph.Path  // the base run's post graph induced on Mask, in (source, target) order
+	Surplus     []*fi.Missing // the surplus events: rules at the frontier of the diff, with their goals in it
+}
+
+// PairDiffProv compares arbitrary pairs of loaded runs (nemo_diffprov_pairs):
+// pairs[e] = {base iteration, other iteration}.  The reference has no
+// counterpart, it compares with run 0 only (differential-provenance.go:22-28,
+// 82-98 are the two queries evaluated here between the pair).  The call is
+// followed by the three fetches of the symmetric diff (INTEGRATION.md §8, §10).
+func (n *Neo4J) PairDiffProv(pairs [][2]uint) ([]*PairDiff, error) {
+	base, other := make([]C.uint32_t, len(pairs)+1), make([]C.uint32_t, len(pairs)+1)
+	for e, p := range pairs {
+		base[e], other[e] = C.uint32_t(p[0]), C.uint32_t(p[1])
+	}
+	if err := n.err(C.nemo_diffprov_pairs(n.ctx, &base[0], &other[0], C.size_t(len(pairs)))); err != nil {
+		return nil, err
+	}
+	// ragged masks: entry e's bytes are out[off[e]:off[e+1]], over the base run's post graph
+	off := make([]C.uint64_t, len(pairs)+1)
+	var used C.uint64_t
+	if err := n.err(C.nemo_fetch_sdiff_masks(n.ctx, &off[0], nil, 0, &used)); err != nil {
+		return nil, err
+	}
+	out := make([]uint8, used+1)
+	if err := n.err(C.nemo_fetch_sdiff_masks(n.ctx, nil, (*C.uint8_t)(&out[0]), used, &used)); err != nil {
+		return nil, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_surplus(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	rows := make([]C.nemo_missing, cnt+1)
+	if err := n.err(C.nemo_fetch_surplus(n.ctx, &rows[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	if err := n.err(C.nemo_pull_edges(n.ctx, 3)); err != nil {
+		return nil, err
+	}
+	res := make([]*PairDiff, len(pairs))
+	for e, p := range pairs {
+		gb := 2*n.runIdx[p[0]] + 1
+		d := &PairDiff{Base: p[0], Other: p[1], Mask: out[off[e]:off[e+1]]}
+		var err error
+		if d.Edges, err = n.paths(uint32(e), gb, nil); err != nil {
+			return nil, err
+		}
+		res[e] = d
+	}
+	// `rule` is local to the entry's base run's post graph; an event's goals are the rule's children in the mask
+	children, flagsOf := map[int]map[uint32][]uint32{}, map[int][]uint8{}
+	for _, row := range rows[:cnt] {
+		e, rule := int(row.entry), uint32(row.rule)
+		gb := 2*n.runIdx[pairs[e][0]] + 1
+		if _, ok := children[gb]; !ok {
+			children[gb] = n.childrenOf(gb)
+			fl, err := n.flags(gb)
+			if err != nil {
+				return nil, err
+			}
+			flagsOf[gb] = fl
+		}
+		m := &fi.Missing{Rule: ruleOf(n.node(gb, rule, flagsOf[gb], nil))}
+		for _, ch := range children[gb][rule] {
+			if res[e].Mask[ch] != 0 {
+				m.Goals = append(m.Goals, goalOf(n.node(gb, ch, flagsOf[gb], nil)))
+			}
+		}
+		res[e].Surplus = append(res[e].Surplus, m)
+	}
+	return res, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

@@ -105,7 +105,8 @@ typedef struct nemo_chain {
 typedef struct nemo_missing {
   uint32_t entry;  /* diff entry (index into the failed-run list)                  */
   uint32_t rule;   /* local index of the rule in run 0's post graph; for a surplus
-                      event: in the entry's own failed run's post graph            */
+                      event: in the entry's own failed run's post graph (after
+                      nemo_diffprov_pairs: in the entry's base run's post graph)   */
 } nemo_missing;
 
 /* ---- run sharding --------------------------------------------
@@ -209,7 +210,10 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *   "dedup_hash_bits"   that grouping buckets by the low k bits of a 128-bit
  *                       content hash, k in 0..128 (default 128; takes effect at the
  *                       next load); every bucket is confirmed by exact comparisons
- *                       (test knob, as "class_hash_bits") */
+ *                       (test knob, as "class_hash_bits")
+ *   "pair_hash_lds_max" largest label table (slots) nemo_diffprov_pairs builds in
+ *                       LDS; larger ones are built in place with global atomics
+ *                       (default and upper bound 16384; 0 = every table in place) */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -374,6 +378,32 @@ int nemo_fetch_sdiff_masks(nemo_ctx *ctx, uint64_t *off /* n+1 */, uint8_t *out,
  * ordered by (entry, rule); `rule` is local to the entry's failed post graph,
  * goals = all S-children of each rule.  out == NULL queries *n_out.         */
 int nemo_fetch_surplus(nemo_ctx *ctx, nemo_missing *out, uint64_t cap, uint64_t *n_out);
+
+/* ---- differential provenance between arbitrary pairs of runs ------------------
+ * The same two queries (the export of differential-provenance.go:22-28 and the
+ * leaf query of :82-98) between any two loaded runs: entry e is the pair
+ * (base_iters[e], other_iters[e]); with gb = the base run's raw post graph,
+ * Bad = goals of gb whose label is no post-goal label of the other run,
+ * S = Fwd*(Bad) ∩ Bwd*(Bad) over gb, surplus events as nemo_diffprov_symmetric
+ * defines them, on gb.  So (f, iteration 0) is nemo_diffprov_symmetric's entry
+ * for f, (iteration 0, f) is nemo_diffprov's per-run entry for f (S = its D
+ * mask, surplus rules = its missing rules), and (x, x) has an empty S.  The
+ * reference has no counterpart: it compares with run 0 only.
+ * Needs nemo_load_corpus and nemo_mark_holds, as the symmetric call does.  Both
+ * lists may name any loaded run, duplicates included (duplicate pairs give
+ * identical results); run 0 need not be loaded; an iteration that is not
+ * loaded is NEMO_ERR_NOTFOUND; n == 0 gives zero entries and NEMO_OK.
+ * The call writes the symmetric diff's state, so its results come through the
+ * same accessors with slot = entry: nemo_fetch_sdiff_masks (ragged, one byte
+ * per node of the entry's base post graph), nemo_fetch_surplus (`rule` is
+ * local to the entry's base run's post graph), nemo_pull_edges(ctx, 3) with
+ * nemo_fetch_pulled(_all) (gb's edges induced on S, in gb's row order).  A later
+ * nemo_diffprov_symmetric or nemo_diffprov_pairs replaces those results;
+ * results of nemo_diffprov stay valid, and the reverse.  The label tables of
+ * the distinct `other` runs are built on the device, on the context's stream
+ * ahead of the walk (an entry against iteration 0 uses the table of the load).
+ * Single-device contexts only (a node context returns NEMO_ERR_STATE).       */
+int nemo_diffprov_pairs(nemo_ctx *ctx, const uint32_t *base_iters, const uint32_t *other_iters, size_t n);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

@@ -288,6 +288,10 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.dedup_hash_bits = value < 0 ? 128 : (int)value;
     return NEMO_OK;
   }
+  if (!strcmp(name, "pair_hash_lds_max")) {  // largest label table (slots) k_lab_hash builds in LDS; 0: every table in place
+    c->opt.pair_hash_lds_max = value < 0 ? LAB_HASH_LDS_SLOTS : (uint32_t)std::min<int64_t>(value, LAB_HASH_LDS_SLOTS);
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;

@@ -1,4 +1,4 @@
-// api_diff.hip — differential provenance: nemo_diffprov*, the symmetric diff and their fetches.
+// api_diff.hip — differential provenance: nemo_diffprov*, the symmetric diff, the pair diff and their fetches.
 #include "ctx.h"
 
 extern "C" {
@@ -496,31 +496,45 @@ int nemo_fetch_diff_support(nemo_ctx *c, uint32_t *out, uint64_t cap) {
 // post-goal label hash: one launch over all entries, on the context's stream,
 // in call order.  Results stay in HBM until fetched; the state is disjoint
 // from nemo_diffprov's.
-int nemo_diffprov_symmetric(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed) {
+//
+// nemo_diffprov_pairs (DESIGN.md §Pair diff) is the same body with the run compared against
+// chosen per entry (`other_iters`, null for the symmetric call): entry e walks base run e's post
+// graph against the label hash of other run e.  An entry against run 0 probes the load's table as
+// the symmetric call does; k_lab_hash builds a table for every other distinct `other` run in the
+// per-call region d_phreg, on the context's stream ahead of the walk.
+static int sdiff_impl(nemo_ctx *c, bool per_pair, const uint32_t *failed_iters, const uint32_t *other_iters,
+                      size_t n_failed) {
+  const char *who = per_pair ? "nemo_diffprov_pairs" : "nemo_diffprov_symmetric";
   if (c && c->node)
-    return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric: single-device contexts only (a node context does not fan it out)");
-  if (!c || (!failed_iters && n_failed)) return NEMO_ERR_INVALID;
-  if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric without a loaded corpus (the last load failed?)");
-  if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "nemo_diffprov_symmetric before nemo_mark_holds");
+    return fail(c, NEMO_ERR_STATE, "%s: single-device contexts only (a node context does not fan it out)", who);
+  if (!c || ((!failed_iters || (per_pair && !other_iters)) && n_failed)) return NEMO_ERR_INVALID;
+  if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "%s without a loaded corpus (the last load failed?)", who);
+  if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "%s before nemo_mark_holds", who);
   HIPCHK(c, hipSetDevice(c->device));
   c->cs.n_sentries = 0;
   c->cs.sd_done = false;
   c->cs.sd_graph.clear();
   c->cs.sd_off.assign(1, 0);
-  if (n_failed == 0 || c->cs.run0 < 0) {  // nothing to compare with: zero entries, as nemo_diffprov
+  // nothing to compare (with): zero entries, as nemo_diffprov; the pairs call names its own `other` runs
+  if (n_failed == 0 || (!per_pair && c->cs.run0 < 0)) {
     c->cs.sd_done = true;
     return NEMO_OK;
   }
   if (n_failed > 0xFFFFFFFFull) return fail(c, NEMO_ERR_LIMIT, "too many diff entries");
-  std::vector<uint32_t> graph(n_failed);
+  std::vector<uint32_t> graph(n_failed), other;
   std::vector<uint64_t> off(n_failed + 1, 0);
   uint32_t n_lds = 0, n_glob = 0;
   // algorithmic bytes per entry: rows both ways (8E + 8V), node word + label + Kahn order (12V),
   // the mask written (V); the three sweeps are counted as traversed edges
   double bytes = 0, edges = 0;
   int rc;
+  if (per_pair) other.resize(n_failed);
   for (size_t e = 0; e < n_failed; e++) {
     uint32_t r;
+    if (per_pair) {
+      if ((rc = run_index(c, other_iters[e], &r))) return rc;
+      other[e] = 2 * r + 1;
+    }
     if ((rc = run_index(c, failed_iters[e], &r))) return rc;
     const uint32_t g = 2 * r + 1;
     const uint64_t V = c->cs.node_off[g + 1] - c->cs.node_off[g], E = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
@@ -533,9 +547,33 @@ int nemo_diffprov_symmetric(nemo_ctx *c, const uint32_t *failed_iters, size_t n_
   }
   const uint64_t total = off[n_failed];
   const bool grow_v = total > c->cs.sd_vcap || !c->cs.d_sdmask, grow_b = n_glob && (total > c->cs.sd_bcap || !c->cs.d_sdbits);
-  if (n_failed > c->cs.sd_ecap || grow_v || grow_b) {
-    // an earlier symmetric call or its pull may still use the buffers
+  // the pairs call's tables (pairs_host.h): one per distinct `other` run but run 0, whose table the load built
+  pairs::Plan plan;
+  if (per_pair) {
+    plan = pairs::plan(other.data(), n_failed, c->cs.node_off.data(), c->cs.run0 >= 0 ? 2 * (int64_t)c->cs.run0 + 1 : -1);
+    if (!plan.ok) return fail(c, NEMO_ERR_LIMIT, "%s: a label table would exceed 2^32 slots", who);
+  }
+  const size_t n_tabs = plan.tab_graph.size();
+  const bool grow_t = per_pair && (n_failed > c->cs.sd_tcap || !c->cs.d_sdtab);
+  const bool grow_h = plan.words > c->cs.ph_cap;
+  if (n_failed > c->cs.sd_ecap || grow_v || grow_b || grow_t || grow_h) {
+    // an earlier symmetric / pairs call or its pull may still use the buffers
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (grow_t) {  // entry descriptors, then table descriptors (at most one per entry)
+      dfree(c, c->cs.d_sdtab);
+      c->cs.d_sdtab = nullptr;
+      c->cs.sd_tcap = 0;
+      const uint64_t cap = (n_failed + 63) & ~(uint64_t)63;
+      if ((rc = dalloc(c, &c->cs.d_sdtab, 2 * cap))) return rc;
+      c->cs.sd_tcap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+    }
+    if (grow_h) {  // the table region, grown like d_sdmask: exactly the largest request so far
+      dfree(c, c->cs.d_phreg);
+      c->cs.d_phreg = nullptr;
+      c->cs.ph_cap = 0;
+      if ((rc = dalloc(c, &c->cs.d_phreg, plan.words))) return rc;
+      c->cs.ph_cap = plan.words;
+    }
     if (n_failed > c->cs.sd_ecap) {
       dfree(c, c->cs.d_sdgraph);
       dfree(c, c->cs.d_sdoff);
@@ -572,11 +610,33 @@ int nemo_diffprov_symmetric(nemo_ctx *c, const uint32_t *failed_iters, size_t n_
   HIPCHK(c, hipMemcpyAsync(c->cs.d_sdgraph, graph.data(), n_failed * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->cs.d_sdoff, off.data(), (n_failed + 1) * 8, hipMemcpyHostToDevice, s));
   nemo::launch_zero(c->cs.d_sdn, 4, s);
+  std::vector<nemo::LabTab> tabs;  // (kept in sd_tabs below, as graph and off are: the uploads read them)
+  if (per_pair) {
+    // [entries] the table each entry probes, then [tables] the tables k_lab_hash fills
+    tabs.resize(n_failed + n_tabs);
+    for (size_t t = 0; t < n_tabs; t++)
+      tabs[n_failed + t] = {c->cs.d_phreg + plan.tab_off[t], plan.tab_mask[t], plan.tab_graph[t]};
+    for (size_t e = 0; e < n_failed; e++)
+      tabs[e] = plan.entry_tab[e] == PAIRS_SHARED ? nemo::LabTab{c->cs.d_r0hkey, c->cs.r0hmask, other[e]}
+                                                   : tabs[n_failed + plan.entry_tab[e]];
+    HIPCHK(c, hipMemcpyAsync(c->cs.d_sdtab, tabs.data(), tabs.size() * sizeof(nemo::LabTab), hipMemcpyHostToDevice, s));
+    // tables of at most pair_hash_lds_max slots are built in LDS; the launch's LDS is the largest of them
+    const uint32_t lds_max = c->opt.pair_hash_lds_max;
+    uint32_t lds_slots = 0;
+    for (size_t t = 0; t < n_tabs; t++)
+      if (plan.tab_mask[t] < lds_max) lds_slots = std::max(lds_slots, plan.tab_mask[t] + 1u);
+    // algorithmic bytes: node word + label of every hashed graph, and the tables written
+    if (n_tabs && (rc = timed(c, "k_lab_hash", 8.0 * (double)plan.nodes + 4.0 * (double)plan.words, 0, [&] {
+           nemo::launch_lab_hash(c->cs.dc, c->cs.d_sdtab + n_failed, (uint32_t)n_tabs, lds_max, lds_slots, s);
+         })))
+      return rc;
+  }
   nemo::SdiffArgs a{};
   a.graph = c->cs.d_sdgraph;
   a.off = c->cs.d_sdoff;
   a.r0hkey = c->cs.d_r0hkey;
   a.r0hmask = c->cs.r0hmask;
+  a.tabs = per_pair ? c->cs.d_sdtab : nullptr;
   a.bits = c->cs.d_sdbits;
   a.depth = c->cs.d_sddepth;
   a.mask = c->cs.d_sdmask;
@@ -587,9 +647,18 @@ int nemo_diffprov_symmetric(nemo_ctx *c, const uint32_t *failed_iters, size_t n_
     return rc;
   c->cs.sd_graph = std::move(graph);
   c->cs.sd_off = std::move(off);
+  c->cs.sd_tabs = std::move(tabs);
   c->cs.n_sentries = (uint32_t)n_failed;
   c->cs.sd_done = true;
   return NEMO_OK;
+}
+
+int nemo_diffprov_symmetric(nemo_ctx *c, const uint32_t *failed_iters, size_t n_failed) {
+  return sdiff_impl(c, false, failed_iters, nullptr, n_failed);
+}
+
+int nemo_diffprov_pairs(nemo_ctx *c, const uint32_t *base_iters, const uint32_t *other_iters, size_t n) {
+  return sdiff_impl(c, true, base_iters, other_iters, n);
 }
 
 int nemo_fetch_sdiff_masks(nemo_ctx *c, uint64_t *off, uint8_t *out, uint64_t cap, uint64_t *n_used) {

@@ -20,6 +20,7 @@
 #include "gdedup_host.h"
 #include "internal.h"
 #include "node.h"
+#include "pairs_host.h"
 
 struct Agg {
   uint64_t launches = 0;
@@ -105,6 +106,7 @@ struct Options {
   int class_hash_bits = 128;  // nemo_diff_classes buckets by the low k bits of the hash (test knob: forces collisions)
   bool graph_dedup = true;    // option graph_dedup: the per-graph kernels run on one graph per distinct content
   int dedup_hash_bits = 128;  // the load's duplicate classes bucket by the low k bits of the hash (test knob)
+  uint32_t pair_hash_lds_max = LAB_HASH_LDS_SLOTS;  // largest label table (slots) k_lab_hash builds in LDS (0: none)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -212,6 +214,13 @@ struct CorpusState {
   uint64_t *d_sdoff = nullptr;
   uint8_t *d_sdmask = nullptr, *d_sdbits = nullptr;
   int32_t *d_sddepth = nullptr;
+  // nemo_diffprov_pairs (the same state, and): the entries' and the tables' descriptors, and the
+  // per-call region k_lab_hash builds the `other` runs' label tables in (pairs_host.h); grow only
+  nemo::LabTab *d_sdtab = nullptr;   // [2 sd_tcap] entry -> its table, then the tables of the call
+  uint32_t sd_tcap = 0;
+  std::vector<nemo::LabTab> sd_tabs;  // the last call's upload
+  uint32_t *d_phreg = nullptr;       // [ph_cap] u32 slots
+  uint64_t ph_cap = 0;
 
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them

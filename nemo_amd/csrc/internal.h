@@ -123,14 +123,24 @@ struct DxArgs {
   DxImg img[2];              // walk images: Kahn order (Fwd*, depth), reversed (Bwd*)
 };
 
-// One nemo_diffprov_symmetric call (k_sdiff.hip): entry e walks its own graph
-// graph[e] (the failed run's post graph); masks, bits and depths are ragged,
+// A post graph's goal labels, open-addressed: key = label + 1 (0 empty), slot hash_label(label) &
+// mask, linear probing.  k_lab_hash builds one per distinct `other` run of nemo_diffprov_pairs (the
+// layout of the load's run-0 table, load_host.h); sdiff_mark_bad probes entry e's.
+struct LabTab {
+  uint32_t *key;            // [mask + 1], 16-byte aligned
+  uint32_t mask;            // table size - 1 (power of two, >= 15)
+  uint32_t graph;           // the post graph whose goals it holds
+};
+
+// One nemo_diffprov_symmetric / nemo_diffprov_pairs call (k_sdiff.hip): entry e walks its own graph
+// graph[e] (the failed / base run's post graph); masks, bits and depths are ragged,
 // entry e's slice starts at off[e] (off[n] = the sum of the entries' nodes).
 struct SdiffArgs {
   const uint32_t *graph;    // [entries] the entry's graph gf
   const uint64_t *off;      // [entries + 1] first node of the entry's slices
   const uint32_t *r0hkey;   // run 0's post-goal labels, open-addressed: key = label + 1 (0 empty)
   uint32_t r0hmask;         // table size - 1 (power of two)
+  const LabTab *tabs;       // [entries] the pairs call: entry e probes tabs[e] (null: every entry the run-0 table)
   uint8_t *bits;            // [off[n]] node bits of the global tier (null: no such entry)
   int32_t *depth;           // [off[n]] depths (both tiers; only S nodes touch them)
   uint8_t *mask;            // [off[n]] S masks (output)
@@ -212,6 +222,12 @@ void launch_diff_expand(uint8_t *mask, const uint8_t *umask, const uint32_t *map
 // n_lds / n_glob: entries inside / past k_diff_lds's caps (host counts; an empty tier is not launched)
 void launch_sdiff(const DevCorpus &c, const SdiffArgs &a, uint32_t n_entries, uint32_t n_lds, uint32_t n_glob,
                   hipStream_t s);
+// tabs[t].key of every table filled from the goals of tabs[t].graph: tables of at most lds_max
+// slots are built in LDS (0: none; lds_slots: the largest of them, the launch's LDS size), the
+// others in place
+#define LAB_HASH_LDS_SLOTS 16384u  // the LDS path's budget: 64 KB, two workgroups per CU
+void launch_lab_hash(const DevCorpus &c, const LabTab *tabs, uint32_t n_tabs, uint32_t lds_max, uint32_t lds_slots,
+                     hipStream_t s);
 uint32_t dclass_rows_per_block(uint64_t V0, uint32_t nu);
 void launch_dclass_hash(const DclassArgs &a, hipStream_t s);
 // verdict[k] = 1 iff rows pairs[2k] and pairs[2k + 1] (sources) have the same membership at every node

@@ -98,6 +98,7 @@ def lib():
             "nemo_fetch_diff_classes": ([vp, vp, vp, u64, P(u64)], i32),
             "nemo_fetch_diff_support": ([vp, vp, u64], i32),
             "nemo_diffprov_symmetric": ([vp, vp, sz], i32),
+            "nemo_diffprov_pairs": ([vp, vp, vp, sz], i32),
             "nemo_fetch_sdiff_masks": ([vp, vp, vp, u64, P(u64)], i32),
             "nemo_fetch_surplus": ([vp, vp, u64, P(u64)], i32),
             "nemo_triggers": ([vp], i32),
@@ -275,6 +276,18 @@ class Engine:
         f = np.ascontiguousarray(failed, dtype=np.uint32)
         self._chk(self.L.nemo_diffprov_symmetric(self.h, _p(f), len(f)))
         self._n_sym = len(f) if 0 in set(int(x) for x in self.corpus.iteration) else 0
+
+    def diffprov_pairs(self, base: Sequence[int], other: Sequence[int]) -> None:
+        """nemo_diffprov_pairs: for every pair (base[e], other[e]) of loaded runs, the part of the base
+        run's post provenance that the other run lacks.  sdiff_masks(), surplus() and pull(3) then
+        return its results, slot = entry, over the base run's post graph."""
+        b = np.ascontiguousarray(base, dtype=np.uint32)
+        o = np.ascontiguousarray(other, dtype=np.uint32)
+        if len(b) != len(o):
+            raise ValueError("diffprov_pairs: base and other differ in length")
+        self._n_sym = 0
+        self._chk(self.L.nemo_diffprov_pairs(self.h, _p(b), _p(o), len(b)))
+        self._n_sym = len(b)
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
         """nemo_goal_labels: [n, label...] of a run's goal labels into device memory."""

@@ -392,12 +392,32 @@ class Neo4J:
     def _surplus(self, failedRuns: Sequence[int]) -> List[DotGraph]:
         """The symmetric half: S masks, surplus events (kept in self.SurplusEvents) and the
         marked DOT of every failed run."""
-        c = self.Runs
         self.eng.diffprov_symmetric(failedRuns)
+        dots, self.SurplusEvents = self._surplus_dots(failedRuns)
+        return dots
+
+    def PairDiffProv(self, pairs: Sequence[Tuple[int, int]]) -> List[dict]:
+        """Differential provenance between arbitrary pairs of runs (nemo_diffprov_pairs).  It has
+        no reference counterpart: differential-provenance.go compares with run 0 only.  `pairs` holds
+        (base iteration, other iteration); one record per pair, in order: {"Base", "Other", "Dot": the
+        base run's createDOT post graph with the part the other run lacks marked
+        (dot.create_surplus_dot, as CreateNaiveDiffProv(True, ...) marks a failed run's), "Surplus": the
+        surplus events as fi.Missing records}.  The results of a CreateNaiveDiffProv(True, ...) on the
+        device are replaced; self.SurplusEvents is left as it is."""
+        pairs = [(int(b), int(o)) for b, o in pairs]
+        base = [b for b, _ in pairs]
+        self.eng.diffprov_pairs(base, [o for _, o in pairs])
+        dots, events = self._surplus_dots(base)
+        return [{"Base": b, "Other": o, "Dot": dots[e], "Surplus": events[e]} for e, (b, o) in enumerate(pairs)]
+
+    def _surplus_dots(self, failedRuns: Sequence[int]):
+        """(marked DOTs, surplus events) of the last symmetric / pairs call, whose entries walked the
+        post graphs of failedRuns."""
+        c = self.Runs
         masks = self.eng.sdiff_masks()
         rows = self.eng.surplus()
         self.eng.pull(3)
-        self.SurplusEvents = [[] for _ in failedRuns]
+        events: List[List[Missing]] = [[] for _ in failedRuns]
         dots = []
         for e, f in enumerate(failedRuns):
             gf = self._g(int(f), "post")
@@ -411,12 +431,12 @@ class Neo4J:
                 for ch in sorted(int(x) for x in dst[src == rule]):
                     if mask[ch]:
                         m.Goals.append(self._goal(self._node(gf, ch)))
-                self.SurplusEvents[e].append(m)
+                events[e].append(m)
                 ids.add(m.Rule.ID)
                 ids.update(gl.ID for gl in m.Goals)
             s_nodes = [self._node(gf, int(i)) for i in np.nonzero(mask)[0]]
             dots.append(create_surplus_dot(self._edges(None, gf), s_nodes, s_edges, ids))
-        return dots
+        return dots, events
 
     # ---- corrections.go / extensions.go -----------------------------------------
     def _trigger_rows(self):

@@ -9,6 +9,13 @@ timing groups (HIP events around the launches).  Prints one JSON line: milliseco
 algorithmic bytes (DESIGN.md §Symmetric diff), the fraction of HBM peak as bench.py computes it
 (bytes / time / 8000 GB/s), and the time per graph of the three kernels.
 
+--pairs: instead, three legs on the same corpus and entries, in one process and with the same method
+(HIP events around the launches of the k_lab_hash and k_sdiff groups): (a) nemo_diffprov_symmetric,
+(b) nemo_diffprov_pairs with every `other` = iteration 0 (the load's shared table, nothing built),
+(c) nemo_diffprov_pairs with a distinct good `other` per entry (one table per entry).  The legs
+alternate `--rounds` times; prints one JSON line with every round's milliseconds per call and the
+table memory of (c).
+
 Reads nothing but the synthetic generator's output; needs a GPU (no fallback).
 """
 import argparse
@@ -38,14 +45,73 @@ def role_exchanged(corpus):
     return ex, [int(it[r]) for r in range(corpus.n_runs) if corpus.status[r] == "success"]
 
 
+def pairs_legs(ex, entries, steps, warmup, rounds):
+    """The three legs of --pairs, alternating; per leg and round the groups' ms per call."""
+    n = len(entries)
+    distinct = entries[1:] + entries[:1]  # entry e against the next good run: n distinct `other` runs
+    legs = {"a_symmetric": lambda eng: eng.diffprov_symmetric(entries),
+            "b_pairs_shared": lambda eng: eng.diffprov_pairs(entries, [0] * n),
+            "c_pairs_distinct": lambda eng: eng.diffprov_pairs(entries, distinct)}
+    # the region of (c): one table per entry, the smallest power of two >= twice the other graph's nodes (>= 16)
+    slots = 0
+    for it in distinct:
+        v, cap = ex.graph_size(2 * ex.run_index(it) + 1), 16
+        while cap < 2 * v:
+            cap *= 2
+        slots += cap
+    out = {"runs": ex.n_runs, "entries": n, "steps": steps, "rounds": rounds, "c_tables": n,
+           "c_table_bytes": 4 * slots, "legs": {k: [] for k in legs}}
+    eng = E.Engine(0)
+    try:
+        eng.load(ex)
+        eng.mark()
+        ref = None
+        for name, call in legs.items():
+            for _ in range(warmup):
+                call(eng)
+            eng.synchronize()
+            masks = eng.sdiff_masks()
+            if name == "a_symmetric":
+                ref = masks
+                out["entries_nonempty"] = sum(1 for m in masks if m.any())
+            elif name == "b_pairs_shared":
+                out["b_equals_a"] = all(np.array_equal(x, y) for x, y in zip(ref, masks))
+            else:
+                out["c_entries_nonempty"] = sum(1 for m in masks if m.any())
+        eng.set_timing(True)
+        eng.set_timing_groups(["k_lab_hash", "k_sdiff"])
+        for _ in range(rounds):
+            for name, call in legs.items():
+                eng.reset_timings()
+                for _ in range(steps):
+                    call(eng)
+                eng.synchronize()
+                t = eng.timings()
+                row = {}
+                for g in ("k_lab_hash", "k_sdiff"):
+                    if g in t and t[g]["launches"]:
+                        ms = t[g]["ms"] / t[g]["launches"]
+                        gb = t[g]["bytes"] / t[g]["launches"]
+                        row[g] = {"ms_per_call": round(ms, 4), "bytes": gb, "gbs": round(gb / ms / 1e6, 1)}
+                out["legs"][name].append(row)
+    finally:
+        eng.close()
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--pairs", action="store_true", help="time symmetric / pairs-shared / pairs-distinct instead")
+    ap.add_argument("--rounds", type=int, default=3, help="--pairs: alternations of the three legs")
     a = ap.parse_args()
     corpus, _ = synth.generate(a.runs, **synth.CONFIGS["c3"])
     ex, entries = role_exchanged(corpus)
+    if a.pairs:
+        pairs_legs(ex, entries, a.steps, a.warmup, a.rounds)
+        return
     success = list(entries)
     eng = E.Engine(0)
     try:
