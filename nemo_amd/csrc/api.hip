@@ -119,6 +119,9 @@ int nemo_ctx_create(int device, nemo_ctx **out) {
 }
 
 static void release_corpus(nemo_ctx *c) {
+  if (getenv("NEMO_LOAD_DEBUG"))
+    fprintf(stderr, "release_corpus: since load %llu dalloc, %llu dfree, size hash %016llx\n",
+            (unsigned long long)c->call_dalloc_n, (unsigned long long)c->call_dfree_n, (unsigned long long)c->call_hash);
   drop_cache(c);  // blocks no allocation took since the last load
   for (void *p : c->allocs) {  // kept for the next load
     auto b = c->alloc_bytes.find(p);
@@ -330,7 +333,7 @@ uint64_t nemo_num_edges(const nemo_ctx *c) { return c ? (c->node ? node_num_edge
 // tier's graphs stay cheap.
 static void set_global_block(nemo_ctx *c) {
   uint32_t deep = 0;
-  for (uint32_t g = 0; g < c->cs.G; g++) deep += (c->cs.node_off[g + 1] - c->cs.node_off[g]) >= 65536u;
+  for (uint32_t g = 0; g < c->cs.G; g++) deep += c->cs.nv(g) >= 65536u;
   c->cs.dc.gblock = c->opt.gblock_force ? c->opt.gblock_force : ((uint64_t)deep * 8u >= c->cs.G && deep ? 1024u : NEMO_BLOCK);
 }
 
@@ -346,8 +349,8 @@ static Tier fit_tier(nemo_ctx *c, uint64_t vmax, uint64_t emax, uint32_t lcap, T
   std::vector<std::pair<uint32_t, uint32_t>> ve;
   ve.reserve(c->cs.G);
   for (uint32_t g = 0; g < c->cs.G; g++) {
-    const uint64_t v = c->cs.node_off[g + 1] - c->cs.node_off[g], e = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
-    if (v <= std::min<uint64_t>(vmax, c->opt.lds_limit) && e <= emax) ve.push_back({(uint32_t)v, (uint32_t)e});
+    const uint64_t v = c->cs.nv(g), e = c->cs.ne(g);
+    if (v <= vmax && e <= emax) ve.push_back({(uint32_t)v, (uint32_t)e});
   }
   std::sort(ve.begin(), ve.end());
   uint32_t cv = 0, ce = 0, em = 0;
@@ -370,8 +373,9 @@ static Tier fit_tier(nemo_ctx *c, uint64_t vmax, uint64_t emax, uint32_t lcap, T
 static void set_lds_tier(nemo_ctx *c) {
   // k_proto_lds: edges in source Kahn order + level offsets (<= 512 levels), node bytes, chains; three
   // 512-thread workgroups per CU
+  const uint64_t vcap = std::min<uint64_t>(16384, c->opt.lds_limit), vcap_pull = std::min<uint64_t>(24u * 256u, c->opt.lds_limit);
   const Tier tp = fit_tier(
-      c, 16384, 65535, 512u,
+      c, vcap, 65535, 512u,
       [](uint32_t v, uint32_t e, uint32_t l, uint32_t w) { return lds_tier_bytes(v, e, l, w); },
       160u * 1024u / 3u - 256u);
   c->cs.dc.lds_v = tp.v;
@@ -379,21 +383,21 @@ static void set_lds_tier(nemo_ctx *c) {
   c->cs.dc.lds_l = tp.l;
   c->cs.dc.lds_bytes = tp.bytes;
   // k_marksimp: node word + two node bytes (the edge list stays in registers / HBM); (src << 16 | dst) pairs
-  c->cs.dc.t_ms = fit_tier(c, 16384, 65535, NO_LEVEL_CAP, [](uint32_t v, uint32_t, uint32_t, uint32_t w) {
+  c->cs.dc.t_ms = fit_tier(c, vcap, 65535, NO_LEVEL_CAP, [](uint32_t v, uint32_t, uint32_t, uint32_t w) {
     return marksimp_bytes(v, w);
   });
   // k_diff_lds: u16 CSR both ways + rule bitmap + node bits (Kahn order and depths stay in HBM)
-  c->cs.dc.t_diff = fit_tier(c, 16384, 65535, NO_LEVEL_CAP, [](uint32_t v, uint32_t e, uint32_t l, uint32_t) {
+  c->cs.dc.t_diff = fit_tier(c, vcap, 65535, NO_LEVEL_CAP, [](uint32_t v, uint32_t e, uint32_t l, uint32_t) {
     return diff_lds_bytes(v, e, l);
   });
   // k_pull_lds: forward u16 CSR + liveness bitmap (per-node counts in registers: 24 nodes per thread)
-  c->cs.dc.t_pull = fit_tier(c, 24u * 256u, 65535, NO_LEVEL_CAP, [](uint32_t v, uint32_t e, uint32_t, uint32_t) {
+  c->cs.dc.t_pull = fit_tier(c, vcap_pull, 65535, NO_LEVEL_CAP, [](uint32_t v, uint32_t e, uint32_t, uint32_t) {
     return pull_lds_bytes(v, e);
   });
   c->cs.tierV = c->cs.tierE = 0;  // k_marksimp's graphs (the deferred markConditionHolds)
   c->cs.ms_rest = c->cs.pull_rest = 0;  // graphs the per-graph global-tier kernels must take (none: not launched)
   for (uint32_t g = 0; g < c->cs.G; g++) {
-    const uint64_t v = c->cs.node_off[g + 1] - c->cs.node_off[g], e = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+    const uint64_t v = c->cs.nv(g), e = c->cs.ne(g);
     const bool ms = tier_fits(c->cs.dc.t_ms, (uint32_t)std::min<uint64_t>(v, ~0u), (uint32_t)std::min<uint64_t>(e, ~0u), 0);
     if (ms) {
       c->cs.tierV += (double)v;
@@ -410,23 +414,12 @@ static void set_lds_tier(nemo_ctx *c) {
 // (k_load.hip build_tier_bytes) keeps four workgroups on a CU.
 #define BUILD_TIER_BUDGET (160u * 1024u / 4u - 64u)
 static void set_build_tier(nemo_ctx *c) {
-  std::vector<std::pair<uint32_t, uint32_t>> ve;
-  ve.reserve(c->cs.G);
-  for (uint32_t g = 0; g < c->cs.G; g++) {
-    const uint64_t v = c->cs.node_off[g + 1] - c->cs.node_off[g], e = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
-    if (v <= std::min<uint64_t>(16384, c->opt.build_limit) && e <= 32u * NEMO_BLOCK) ve.push_back({(uint32_t)v, (uint32_t)e});
-  }
-  std::sort(ve.begin(), ve.end());
-  uint32_t cv = 0, ce = 0, emax = 0;
-  for (auto &x : ve) {
-    emax = std::max(emax, x.second);
-    if (nemo::build_tier_bytes(x.first, emax) > BUILD_TIER_BUDGET) break;
-    cv = x.first;
-    ce = emax;
-  }
-  c->cs.dc.bld_v = cv;
-  c->cs.dc.bld_e = ce;
-  c->cs.dc.bld_bytes = cv ? nemo::build_tier_bytes(cv, ce) : 0;
+  const Tier t = fit_tier(
+      c, std::min<uint64_t>(16384, c->opt.build_limit), 32u * NEMO_BLOCK, NO_LEVEL_CAP,
+      [](uint32_t v, uint32_t e, uint32_t, uint32_t) { return nemo::build_tier_bytes(v, e); }, BUILD_TIER_BUDGET);
+  c->cs.dc.bld_v = t.v;
+  c->cs.dc.bld_e = t.e;
+  c->cs.dc.bld_bytes = t.bytes;
 }
 
 // Upload parts of a corpus whose edges are mostly big graphs (nemo_load_corpus, option load_parts):
@@ -476,7 +469,7 @@ static int device_load(nemo_ctx *c, const LoadParts *lp = nullptr) {
   // graphs within k_build's LDS caps vs the global tier
   double Vb = 0, Eb = 0, Vp = 0, Ep = 0;
   for (uint32_t g = 0; g < c->cs.G && c->cs.dc.bld_bytes; g++) {
-    const uint64_t v = c->cs.node_off[g + 1] - c->cs.node_off[g], e = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+    const uint64_t v = c->cs.nv(g), e = c->cs.ne(g);
     if (v <= c->cs.dc.bld_v && e <= c->cs.dc.bld_e) {
       Vb += (double)v;
       Eb += (double)e;
@@ -585,7 +578,7 @@ int Load::load_plan_glob() {
   std::vector<uint64_t> off(G, ~0ull);
   uint64_t words = 0;
   for (uint32_t g = 0; g < G; g++) {
-    const uint64_t v = s.node_off[g + 1] - s.node_off[g], e = s.edge_off[g + 1] - s.edge_off[g];
+    const uint64_t v = s.nv(g), e = s.ne(g);
     if (v >= c->opt.glob_min_v && v > 0) {
       off[g] = words;
       words += (nemo::glob_words(v, e) + 63) & ~63ull;
@@ -627,7 +620,7 @@ int Load::load_plan_chain_tmp() {
   std::vector<uint64_t> off(G, 0);
   uint64_t words = 0;
   for (uint32_t g = 0; g < G; g++) {
-    const uint64_t v = s.node_off[g + 1] - s.node_off[g];
+    const uint64_t v = s.nv(g);
     off[g] = words;
     if (!(v >= c->opt.glob_min_v && v > 0)) words += 5 * v;
   }
@@ -645,7 +638,7 @@ int Load::load_plan_big() {
   std::vector<uint32_t> big;
   uint64_t emax = 0;
   for (uint32_t g = 0; g < G; g++) {
-    const uint64_t v = s.node_off[g + 1] - s.node_off[g], e = s.edge_off[g + 1] - s.edge_off[g];
+    const uint64_t v = s.nv(g), e = s.ne(g);
     if (v < NEMO_CSR_BIG) continue;
     big.push_back(g);
     emax = std::max(emax, e);
@@ -664,7 +657,7 @@ int Load::load_plan_big() {
   bool fits = !big.empty();
   for (size_t b = 0; b < big.size(); b++) {
     const uint32_t g = big[b];
-    const uint64_t v = s.node_off[g + 1] - s.node_off[g], e = s.edge_off[g + 1] - s.edge_off[g];
+    const uint64_t v = s.nv(g), e = s.ne(g);
     const uint64_t nbk = (v + CB_NB - 1) / CB_NB, nck = (e + CB_CHUNK - 1) / CB_CHUNK;
     fits &= nbk <= CB_MAXB;
     hoff[b + 1] = hoff[b] + std::max<uint64_t>(nbk * nck, 1);
@@ -684,7 +677,7 @@ int Load::load_plan_big() {
   }
   s.big_chunks = (uint32_t)std::min<uint64_t>(128, std::max<uint64_t>(1, (emax + 16383) / 16384));
   uint64_t vpost = 0;  // k_pg_* chunks: the largest post graph
-  for (uint32_t g = 1; g < G; g += 2) vpost = std::max<uint64_t>(vpost, s.node_off[g + 1] - s.node_off[g]);
+  for (uint32_t g = 1; g < G; g += 2) vpost = std::max<uint64_t>(vpost, s.nv(g));
   d.pg_chunks = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, vpost / 16384));
   return NEMO_OK;
 }
@@ -724,7 +717,7 @@ int Load::load_upload() {
   bool ok = E && d.cb_hist && P > 1 && d.n_big >= 2 * P && c->opt.topo_ell_off && s.bigE >= 0.5 * (double)E;
   for (uint32_t b = 0; b < d.n_big && ok; b++) {  // no big graph of k_build's (its redo flag comes later)
     const uint32_t g = s.big_host[b];
-    const uint64_t v = s.node_off[g + 1] - s.node_off[g], e = s.edge_off[g + 1] - s.edge_off[g];
+    const uint64_t v = s.nv(g), e = s.ne(g);
     ok = !(d.bld_bytes && v <= d.bld_v && e <= d.bld_e);
   }
   if (ok) {
@@ -775,7 +768,7 @@ int Load::load_upload() {
 int Load::load_run0_tables() {
   if (s.run0 < 0) return NEMO_OK;
   hipStream_t st = c->stream;
-  const uint32_t g0 = 2 * s.run0 + 1;
+  const uint32_t g0 = s.g0();
   const R0Tables t = r0_tables(s, in);
   const size_t nl = t.l.size(), hcap = t.hkey.size(), nlab = t.dense.size();
   s.n_r0lab = (uint32_t)nl;
@@ -797,8 +790,7 @@ int Load::load_run0_tables() {
   }
   HIPCHK(c, hipStreamSynchronize(st));  // the tables go out of scope
   // the multi-entry diff's relayout of g0: every row must fit one walk window
-  const uint64_t n0 = s.node_off[g0], nv = s.node_off[g0 + 1] - n0;
-  const uint64_t e0 = s.edge_off[g0], ne = s.edge_off[g0 + 1] - e0;
+  const uint64_t nv = s.V0(), e0 = s.edge_off[g0], ne = s.E0();
   std::vector<uint32_t> din(nv, 0), dout(nv, 0);
   uint32_t maxdeg = 0;
   for (uint64_t e = e0; e < e0 + ne; e++) {
@@ -833,15 +825,15 @@ int Load::load_run0_tables() {
 // degree, post rows (g, r) <= edges, async rules <= nodes (corrections.go:30-34,121-125)
 int Load::load_trigger_caps() {
   if (s.run0 < 0) return NEMO_OK;
-  const uint32_t gp = 2 * s.run0, gq = gp + 1;
-  const uint64_t v0 = s.node_off[gp], nv = s.node_off[gp + 1] - v0;
+  const uint32_t gp = 2 * s.run0;
+  const uint64_t nv = s.nv(gp);
   std::vector<uint32_t> din(nv, 0), dout(nv, 0);
   for (uint64_t e = s.edge_off[gp]; e < s.edge_off[gp + 1]; e++) {
     if (in->edge_src[e] < nv) dout[in->edge_src[e]]++;
     if (in->edge_dst[e] < nv) din[in->edge_dst[e]]++;
   }
   for (uint64_t v = 0; v < nv; v++) s.tcap[0] += (uint64_t)din[v] * dout[v];
-  s.tcap[1] = s.edge_off[gq + 1] - s.edge_off[gq];
+  s.tcap[1] = s.E0();
   s.tcap[2] = nv;
   A(s.d_tpre, 3 * s.tcap[0] + 3), A(s.d_tpost, 2 * s.tcap[1] + 2), A(s.d_tasync, s.tcap[2] + 1);
   return rc;
@@ -883,7 +875,7 @@ static int load_graph_classes(nemo_ctx *c, bool dbg) {
   }
   std::vector<uint8_t> eligible(G);
   for (uint32_t g = 0; g < G; g++) {
-    const uint64_t v = s.node_off[g + 1] - s.node_off[g];
+    const uint64_t v = s.nv(g);
     eligible[g] = v < NEMO_CSR_BIG && v < c->opt.glob_min_v;
   }
   gdedup::Plan p = gdedup::plan(ref.rep(), eligible, s.node_off.data());
@@ -898,7 +890,7 @@ static int load_graph_classes(nemo_ctx *c, bool dbg) {
     double dv = 0, de = 0, dvp = 0, dep = 0;
     for (uint32_t k = 0; k < s.gd_npairs; k++) {
       const uint32_t g = p.pairs[2 * k];
-      const double v = (double)(s.node_off[g + 1] - s.node_off[g]), e = (double)(s.edge_off[g + 1] - s.edge_off[g]);
+      const double v = (double)s.nv(g), e = (double)s.ne(g);
       dv += v, de += e;
       if (g & 1) dvp += v, dep += e;
     }
@@ -956,6 +948,8 @@ int nemo_load_corpus(nemo_ctx *c, const nemo_corpus *in) {
   }
   if (dbg) fprintf(stderr, "nemo_load_corpus: done %.1f ms\n", ms_since());
   c->cs.loaded = true;
+  c->call_dalloc_n = c->call_dfree_n = 0;  // the per-call requests are counted from here (release_corpus)
+  c->call_hash = 0xCBF29CE484222325ull;
   return NEMO_OK;
 }
 
@@ -1227,15 +1221,15 @@ int nemo_debug_copy(nemo_ctx *c, const char *name, void *out, uint64_t offset, u
   if (n == "topo") base = c->cs.dc.topo;
   else if (n == "lvl") base = c->cs.dc.lvl;
   else if (n == "nlv") base = c->cs.dc.nlv;
-  else if (n == "diff_tpos") base = c->cs.d_dtopo;
+  else if (n == "diff_tpos") base = c->cs.d_dtopo.p;
   else if (n == "nlev") base = c->cs.dc.nlev;
   else if (n == "fp") base = c->cs.dc.fp;
   else if (n == "fc") base = c->cs.dc.fc;
   else if (n == "rp") base = c->cs.dc.rp;
   else if (n == "rc") base = c->cs.dc.rc;
   else if (n == "flags") base = c->cs.dc.flags;
-  else if (n == "dbits") base = c->cs.d_dbits;
-  else if (n == "dmask") base = c->cs.d_dmask;
+  else if (n == "dbits") base = c->cs.d_dbits.p;
+  else if (n == "dmask") base = c->cs.d_dmask.p;
   else if (n == "r0lab") base = c->cs.d_r0lab;
   else if (n == "r0idx") base = c->cs.d_r0idx;
   else if (n == "stamps") base = c->cs.dc.stamps;

@@ -40,62 +40,47 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
     if (ins.second) {
       urep[nu] = (uint32_t)e;  // the first entry of each source stands for it (nemo_pull_edges(2))
       src[nu++] = 2 * r + 1;
-      src_bytes += d_labels ? 0.0 : 8.0 * (double)(c->cs.node_off[2 * r + 2] - c->cs.node_off[2 * r + 1]);
+      src_bytes += d_labels ? 0.0 : 8.0 * (double)c->cs.nv(2 * r + 1);
     }
     c->cs.dmap[e] = emap[e] = ins.first->second;
   }
   if (d_labels) src_bytes = 4.0 * (double)labels_cap;  // read once, then L2-resident
   const bool expand = nu < n_failed;
-  const uint32_t g0 = 2 * c->cs.run0 + 1;
-  const uint64_t V0 = c->cs.node_off[g0 + 1] - c->cs.node_off[g0];
-  const uint64_t E0 = c->cs.edge_off[g0 + 1] - c->cs.edge_off[g0];
+  CorpusState &cs = c->cs;
+  const uint64_t V0 = cs.V0(), E0 = cs.E0();
   const bool dx = c->cs.dx_ok && !c->opt.diff_legacy && (c->opt.diff_window != 2 || c->cs.g0_maxdeg <= nemo::dx_max_row_tiny());
   int rc;
   // capacities in whole 64-entry chunks: the per-entry buffers of corpora (batches) with a few more
   // or fewer failed runs are the same size, so the allocation cache hands the same blocks back (a
   // block no load takes is freed at the next load, and hipFree waits for the whole device)
   const uint64_t nf_cap = (n_failed + 63) & ~(uint64_t)63;
-  if (n_failed > c->cs.diff_cap) {
-    for (void *q : {(void *)c->cs.d_dsrc, (void *)c->cs.d_dmask, (void *)c->cs.d_miss, (void *)c->cs.d_dbits, (void *)c->cs.d_dumask,
-                    (void *)c->cs.d_ddepth, (void *)c->cs.d_dtopo})
-      dfree(c, q);
-    c->cs.d_dbits = c->cs.d_dumask = nullptr;
-    c->cs.d_ddepth = nullptr;
-    c->cs.d_dtopo = nullptr;
-    c->cs.legacy_cap = 0;
-    if ((rc = dalloc(c, &c->cs.d_dsrc, 3 * nf_cap))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_dmask, nf_cap * V0))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_miss, 2 * nf_cap * (V0 + 1)))) return rc;
-    c->cs.diff_cap = (uint32_t)nf_cap;
+  auto drop_legacy = [&] { cs.d_dbits.release(c), cs.d_dumask.release(c), cs.d_ddepth.release(c), cs.d_dtopo.release(c); };
+  if (3 * nf_cap > cs.d_dsrc.cap || !cs.d_miss.p) {
+    cs.d_dsrc.release(c), cs.d_dmask.release(c), cs.d_miss.release(c);
+    drop_legacy();  // a larger entry count outgrows it too: it comes back at the next call that needs it
+    if ((rc = cs.d_dsrc.grow(c, 3 * nf_cap)) || (rc = cs.d_dmask.grow(c, nf_cap * V0)) ||
+        (rc = cs.d_miss.grow(c, 2 * nf_cap * (V0 + 1))))
+      return rc;
   }
-  if (!dx && n_failed > c->cs.legacy_cap) {  // the one-workgroup-per-entry kernels' scratch
-    for (void *q : {(void *)c->cs.d_dbits, (void *)c->cs.d_dumask, (void *)c->cs.d_ddepth, (void *)c->cs.d_dtopo}) dfree(c, q);
-    c->cs.d_dbits = c->cs.d_dumask = nullptr;
-    c->cs.d_ddepth = nullptr;
-    c->cs.d_dtopo = nullptr;
-    if ((rc = dalloc(c, &c->cs.d_dbits, nf_cap * V0))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_dumask, nf_cap * V0))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_ddepth, nf_cap * V0))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_dtopo, 4 * V0 + 2 * E0 + 2 + c->cs.n_r0lab))) return rc;
-    c->cs.legacy_cap = (uint32_t)nf_cap;
+  if (!dx && (nf_cap * V0 > cs.d_dbits.cap || !cs.d_dtopo.p)) {  // the one-workgroup-per-entry kernels' scratch
+    drop_legacy();
+    if ((rc = cs.d_dbits.grow(c, nf_cap * V0)) || (rc = cs.d_dumask.grow(c, nf_cap * V0)) ||
+        (rc = cs.d_ddepth.grow(c, nf_cap * V0)) || (rc = cs.d_dtopo.grow(c, 4 * V0 + 2 * E0 + 2 + cs.n_r0lab)))
+      return rc;
   }
   const uint32_t nch = (nu + 63) / 64, w32 = (uint32_t)((V0 + 31) / 32), nu_cap = 64 * nch;
-  if (dx && (nu > c->cs.dx_nu_cap || nch > c->cs.dx_nch_cap)) {
-    for (void *q : {(void *)c->cs.d_dxpb, (void *)c->cs.d_dxsval, (void *)c->cs.d_dxlpl, (void *)c->cs.d_dxw, (void *)c->cs.d_dxfb})
-      dfree(c, q);
-    c->cs.d_dxpb = c->cs.d_dxsval = c->cs.d_dxlpl = c->cs.d_dxfb = nullptr;
-    c->cs.d_dxw = nullptr;
-    c->cs.dx_nu_cap = c->cs.dx_nch_cap = 0;
-    if ((rc = dalloc(c, &c->cs.d_dxpb, (size_t)nu_cap * w32))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_dxsval, (size_t)nu_cap * V0))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_dxlpl, (size_t)nu_cap + nch))) return rc;  // maxima, then the chunks' walk flags
-    if ((rc = dalloc(c, &c->cs.d_dxw, 4 * (size_t)nch * V0))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_dxfb, 8 * (size_t)nch * V0))) return rc;  // 32 bytes per position and chunk
-    c->cs.dx_nu_cap = nu_cap;
-    c->cs.dx_nch_cap = nch;
+  if (dx && nu > cs.dx_nu_cap) {
+    cs.d_dxpb.release(c), cs.d_dxsval.release(c), cs.d_dxlpl.release(c), cs.d_dxw.release(c), cs.d_dxfb.release(c);
+    cs.dx_nu_cap = 0;
+    if ((rc = cs.d_dxpb.grow(c, (uint64_t)nu_cap * w32)) || (rc = cs.d_dxsval.grow(c, (uint64_t)nu_cap * V0)) ||
+        (rc = cs.d_dxlpl.grow(c, (uint64_t)nu_cap + nch)) ||  // maxima, then the chunks' walk flags
+        (rc = cs.d_dxw.grow(c, 4 * (uint64_t)nch * V0)) ||
+        (rc = cs.d_dxfb.grow(c, 8 * (uint64_t)nch * V0)))  // 32 bytes per position and chunk
+      return rc;
+    cs.dx_nu_cap = nu_cap;
   }
-  if (!c->cs.d_nmiss && (rc = dalloc(c, &c->cs.d_nmiss, 1))) return rc;
-  c->cs.d_dmap = c->cs.d_dsrc + n_failed;
+  if ((rc = cs.d_nmiss.grow(c, 1))) return rc;
+  c->cs.d_dmap = c->cs.d_dsrc.p + n_failed;
   c->cs.n_uniq = nu;
   // the diff kernels go on `aux` once `stream` has reached this point (the load /
   // rebuild of the graphs they read is queued there)
@@ -107,9 +92,9 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
     HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
     s = c->aux;
   }
-  nemo::launch_to_host(c->cs.d_dsrc, src, 3 * n_failed * 4, s);  // pinned -> device by a copy kernel (no blit queue)
+  nemo::launch_to_host(c->cs.d_dsrc.p, src, 3 * n_failed * 4, s);  // pinned -> device by a copy kernel (no blit queue)
   HIPCHK(c, hipEventRecord(c->ev_up_dsrc, s));
-  nemo::launch_zero(c->cs.d_nmiss, 4, s);
+  nemo::launch_zero(c->cs.d_nmiss.p, 4, s);
   // HBM lower bound: run 0's post graph once (rows both ways, node word, Kahn
   // order: 8E0 + 16V0 -- every entry re-reads it from L2), each distinct label
   // source and each entry's D mask (V0); the three reachability sweeps per
@@ -121,7 +106,7 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
     a.p = c->cs.dxp;
     a.nu = nu;
     a.nch = nch;
-    a.src = c->cs.d_dsrc;
+    a.src = c->cs.d_dsrc.p;
     a.ref_labels = d_labels;
     a.r0lab = c->cs.d_r0lab;
     a.r0hkey = c->cs.d_r0hkey;
@@ -129,30 +114,30 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
     a.r0hmask = c->cs.r0hmask;
     a.r0dense = c->cs.dxp.r0dense;
     a.nlab = c->cs.nlab;
-    a.pb = c->cs.d_dxpb;
+    a.pb = c->cs.d_dxpb.p;
     a.w32 = w32;
     uint64_t maxsrc = d_labels ? labels_cap : 0;
     for (uint32_t u = 0; u < nu && !d_labels; u++)
-      maxsrc = std::max<uint64_t>(maxsrc, c->cs.node_off[src[u] + 1] - c->cs.node_off[src[u]]);
+      maxsrc = std::max<uint64_t>(maxsrc, cs.nv(src[u]));
     a.lab_per = 8192;  // one workgroup per source up to 8192 nodes: its bitmap stored whole, no atomics
     a.lab_split = (uint32_t)std::max<uint64_t>(1, (maxsrc + a.lab_per - 1) / a.lab_per);
     const size_t plane = (size_t)nch * V0;
-    a.gw = c->cs.d_dxw;
+    a.gw = c->cs.d_dxw.p;
     a.bw = a.gw + plane;
     a.dw = a.bw + plane;
     a.lw = a.dw + plane;
-    a.fb = reinterpret_cast<uint8_t *>(c->cs.d_dxfb);
-    a.sval = c->cs.d_dxsval;
-    a.maxlen = c->cs.d_dxlpl;
-    a.wflag = c->cs.d_dxlpl + c->cs.dx_nu_cap;
-    a.mask = c->cs.d_dmask;
+    a.fb = reinterpret_cast<uint8_t *>(c->cs.d_dxfb.p);
+    a.sval = c->cs.d_dxsval.p;
+    a.maxlen = c->cs.d_dxlpl.p;
+    a.wflag = c->cs.d_dxlpl.p + c->cs.dx_nu_cap;
+    a.mask = c->cs.d_dmask.p;
     a.map = c->cs.d_dmap;
     a.n_entries = (uint32_t)n_failed;
-    a.missing = c->cs.d_miss;
-    a.n_missing = c->cs.d_nmiss;
+    a.missing = c->cs.d_miss.p;
+    a.n_missing = c->cs.d_nmiss.p;
     a.window = c->opt.diff_window;
     a.legacy_lp = c->opt.diff_unfused;
-    a.urep = c->cs.d_dsrc + 2 * n_failed;
+    a.urep = c->cs.d_dsrc.p + 2 * n_failed;
     a.own_mask = nu == n_failed ? 1u : 0u;
     if (c->cs.dx_img_key < 0) {
       // g0 in Kahn order (read the Kahn order, both CSRs and the node words;
@@ -175,8 +160,8 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
     rc = timed_on(c, s, "k_diff", bytes, (double)nu * 3 * E0, [&] { nemo::launch_dx(c->cs.dc, a, s); });
   } else {
     nemo::DiffArgs a;
-    a.g0 = g0;
-    a.src = c->cs.d_dsrc;
+    a.g0 = cs.g0();
+    a.src = c->cs.d_dsrc.p;
     a.ref_labels = d_labels;
     a.r0lab = c->cs.d_r0lab;
     a.r0idx = c->cs.d_r0idx;
@@ -184,24 +169,24 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
     a.r0hkey = c->cs.d_r0hkey;
     a.r0hval = c->cs.d_r0hval;
     a.r0hmask = c->cs.r0hmask;
-    a.bits = c->cs.d_dbits;
-    a.depth = c->cs.d_ddepth;
-    a.tpos = c->cs.d_dtopo;
+    a.bits = c->cs.d_dbits.p;
+    a.depth = c->cs.d_ddepth.p;
+    a.tpos = c->cs.d_dtopo.p;
     a.tinfo = a.tpos + V0;
     a.trp = a.tinfo + V0;
     a.tfp = a.trp + V0 + 1;
     a.trc = a.tfp + V0 + 1;
     a.tfc = a.trc + E0;
     a.r0pos = a.tfc + E0;
-    a.mask = expand ? c->cs.d_dumask : c->cs.d_dmask;
-    a.missing = c->cs.d_miss;
-    a.n_missing = c->cs.d_nmiss;
+    a.mask = expand ? c->cs.d_dumask.p : c->cs.d_dmask.p;
+    a.missing = c->cs.d_miss.p;
+    a.n_missing = c->cs.d_nmiss.p;
     rc = timed_on(c, s, "k_diff", bytes, (double)nu * 3 * E0,
                   [&] {
                     // the Kahn-order relayout only when g0 may fall outside the LDS tier
                     const bool lds = c->cs.dc.t_diff.bytes && V0 <= c->cs.dc.t_diff.v && E0 <= c->cs.dc.t_diff.e;
                     nemo::launch_diff(c->cs.dc, a, nu, lds ? 0u : (uint32_t)V0, s);
-                    if (expand) nemo::launch_diff_expand(c->cs.d_dmask, c->cs.d_dumask, c->cs.d_dmap, V0, (uint32_t)n_failed, s);
+                    if (expand) nemo::launch_diff_expand(c->cs.d_dmask.p, c->cs.d_dumask.p, c->cs.d_dmap, V0, (uint32_t)n_failed, s);
                   });
   }
   if (rc) return rc;
@@ -214,9 +199,9 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
   c->cs.mrows_staged = std::min<uint64_t>(c->mrows_hint, (uint64_t)n_failed * (V0 + 1));
   if ((rc = c->h_mrows.grow(c, 2 * c->cs.mrows_staged + 2))) return rc;
   nemo::HostCopies hc;
-  hc.add(c->h_mask.p, c->cs.d_dmask, n_failed * V0);
-  hc.add(c->h_nmiss.p, c->cs.d_nmiss, 4);
-  hc.add(c->h_mrows.p, c->cs.d_miss, 8 * c->cs.mrows_staged);
+  hc.add(c->h_mask.p, c->cs.d_dmask.p, n_failed * V0);
+  hc.add(c->h_nmiss.p, c->cs.d_nmiss.p, 4);
+  hc.add(c->h_mrows.p, c->cs.d_miss.p, 8 * c->cs.mrows_staged);
   nemo::launch_to_host_multi(hc, s);
   HIPCHK(c, hipEventRecord(c->ev_diff, s));
   c->cs.aux_pending = true;
@@ -245,22 +230,18 @@ int nemo_diffprov_host_labels(nemo_ctx *c, const uint32_t *failed_iters, size_t 
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   if ((rc = join_aux(c))) return rc;  // the previous diff may still read d_hlab
-  if (n_labels + 1 > c->cs.hlab_cap) {
+  if (n_labels + 1 > c->cs.d_hlab.cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dfree(c, c->cs.d_hlab);
-    c->cs.d_hlab = nullptr;
-    c->cs.hlab_cap = 0;
-    if ((rc = dalloc(c, &c->cs.d_hlab, n_labels + 1))) return rc;
-    c->cs.hlab_cap = n_labels + 1;
+    if ((rc = c->cs.d_hlab.grow(c, n_labels + 1))) return rc;
   }
   if ((rc = ensure_event(c, &c->ev_up_hlab))) return rc;
   HIPCHK(c, hipEventSynchronize(c->ev_up_hlab));  // the previous upload has landed (at once if there was none)
   if ((rc = c->h_hlab.grow(c, n_labels + 1))) return rc;
   c->h_hlab.p[0] = (uint32_t)n_labels;
   if (n_labels) memcpy(c->h_hlab.p + 1, labels, n_labels * 4);
-  nemo::launch_to_host(c->cs.d_hlab, c->h_hlab.p, (n_labels + 1) * 4, c->stream);  // pinned -> device by a copy kernel
+  nemo::launch_to_host(c->cs.d_hlab.p, c->h_hlab.p, (n_labels + 1) * 4, c->stream);  // pinned -> device by a copy kernel
   HIPCHK(c, hipEventRecord(c->ev_up_hlab, c->stream));
-  return diffprov_impl(c, failed_iters, n_failed, NEMO_DIFF_REFERENCE, c->cs.d_hlab, n_labels + 1);
+  return diffprov_impl(c, failed_iters, n_failed, NEMO_DIFF_REFERENCE, c->cs.d_hlab.p, n_labels + 1);
 }
 
 int nemo_goal_labels(nemo_ctx *c, uint32_t iteration, int cond, uint32_t *d_out, uint64_t cap) {
@@ -273,7 +254,7 @@ int nemo_goal_labels(nemo_ctx *c, uint32_t iteration, int cond, uint32_t *d_out,
   int rc = run_index(c, iteration, &r);
   if (rc) return rc;
   const uint32_t g = 2 * r + (uint32_t)cond;
-  const uint64_t V = c->cs.node_off[g + 1] - c->cs.node_off[g];
+  const uint64_t V = c->cs.nv(g);
   if (cap < V + 1) return fail(c, NEMO_ERR_INVALID, "label capacity %llu < %llu", (unsigned long long)cap,
                                (unsigned long long)(V + 1));
   HIPCHK(c, hipSetDevice(c->device));
@@ -285,8 +266,7 @@ int nemo_fetch_diff_mask(nemo_ctx *c, uint32_t entry, uint8_t *out, uint64_t cap
   DISPATCH(node_fetch_diff_mask(c, entry, out, cap));
   if (!c || !out) return NEMO_ERR_INVALID;
   if (entry >= c->cs.n_entries) return fail(c, NEMO_ERR_INVALID, "diff entry %u out of range", entry);
-  const uint32_t g0 = 2 * c->cs.run0 + 1;
-  const uint64_t V0 = c->cs.node_off[g0 + 1] - c->cs.node_off[g0];
+  const uint64_t V0 = c->cs.V0();
   if (cap < V0) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(c->ev_diff));
@@ -298,8 +278,7 @@ int nemo_fetch_diff_masks(nemo_ctx *c, uint8_t *out, uint64_t cap) {
   DISPATCH(node_fetch_diff_masks(c, out, cap));
   if (!c || !out) return NEMO_ERR_INVALID;
   if (!c->cs.n_entries) return NEMO_OK;
-  const uint32_t g0 = 2 * c->cs.run0 + 1;
-  const uint64_t n = (uint64_t)c->cs.n_entries * (c->cs.node_off[g0 + 1] - c->cs.node_off[g0]);
+  const uint64_t n = (uint64_t)c->cs.n_entries * c->cs.V0();
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(c->ev_diff));
@@ -312,8 +291,7 @@ int nemo_diff_masks_view(nemo_ctx *c, const uint8_t **masks, uint64_t *n_entries
   if (!c || !masks) return NEMO_ERR_INVALID;
   *masks = nullptr;
   if (n_entries) *n_entries = c->cs.n_entries;
-  const uint32_t g0 = c->cs.run0 >= 0 ? 2 * c->cs.run0 + 1 : 0;
-  if (v0) *v0 = c->cs.run0 >= 0 ? c->cs.node_off[g0 + 1] - c->cs.node_off[g0] : 0;
+  if (v0) *v0 = c->cs.V0();
   if (!c->cs.n_entries) return NEMO_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(c->ev_diff));
@@ -340,7 +318,7 @@ int nemo_fetch_missing(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
   if (nu_rows > c->cs.mrows_staged) {  // more rows than diffprov copied with the masks
     if ((rc = c->h_mrows.grow(c, 2 * (uint64_t)nu_rows + 2))) return rc;
     if ((rc = join_aux(c))) return rc;
-    nemo::launch_to_host(c->h_mrows.p, c->cs.d_miss, 8ull * nu_rows, c->stream);
+    nemo::launch_to_host(c->h_mrows.p, c->cs.d_miss.p, 8ull * nu_rows, c->stream);
     HIPCHK(c, hipEventRecord(c->ev_misc, c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev_misc));
     c->cs.mrows_staged = nu_rows;
@@ -383,7 +361,7 @@ int nemo_diff_classes(nemo_ctx *c) {
   cs.dc_hash.clear();
   cs.dc_rounds = 0;
   const uint32_t n = cs.n_entries, nu = cs.n_uniq;
-  const uint64_t V0 = cs.run0 >= 0 ? cs.node_off[2 * cs.run0 + 2] - cs.node_off[2 * cs.run0 + 1] : 0;
+  const uint64_t V0 = cs.V0();
   cs.dc_support.assign(V0, 0);
   if (!n) {
     cs.dc_done = true;
@@ -394,14 +372,12 @@ int nemo_diff_classes(nemo_ctx *c) {
   if ((rc = ensure_event(c, &c->ev_dclass))) return rc;
   hipStream_t s = cs.diff_stream;  // behind the diff kernels, on whichever stream they ran
   const uint32_t cap = (nu + 63u) & ~63u;
-  if (cap > cs.dc_cap || !cs.d_dcacc) {
-    for (void *q : {(void *)cs.d_dcacc, (void *)cs.d_dcin, (void *)cs.d_dcv}) dfree(c, q);
-    cs.d_dcacc = cs.d_dcin = nullptr;
-    cs.d_dcv = nullptr;
+  if (cap > cs.dc_cap) {
+    cs.d_dcacc.release(c), cs.d_dcin.release(c), cs.d_dcv.release(c);
     cs.dc_cap = 0;
-    if ((rc = dalloc(c, &cs.d_dcacc, 5 * (size_t)cap + V0))) return rc;
-    if ((rc = dalloc(c, &cs.d_dcin, 2 * (size_t)cap))) return rc;
-    if ((rc = dalloc(c, &cs.d_dcv, (size_t)cap))) return rc;
+    if ((rc = cs.d_dcacc.grow(c, 5 * (uint64_t)cap + V0)) || (rc = cs.d_dcin.grow(c, 2 * (uint64_t)cap)) ||
+        (rc = cs.d_dcv.grow(c, cap)))
+      return rc;
     cs.dc_cap = cap;
   }
   if ((rc = c->h_dcin.grow(c, 2 * (uint64_t)cap))) return rc;
@@ -414,17 +390,17 @@ int nemo_diff_classes(nemo_ctx *c) {
     first[cs.dmap[e]] = e;
   }
   nemo::DclassArgs a{};
-  a.mask = cs.d_dmask;
+  a.mask = cs.d_dmask.p;
   a.V0 = V0;
-  a.row = cs.d_dsrc + 2 * (size_t)n;
-  a.weight = cs.d_dcin;
+  a.row = cs.d_dsrc.p + 2 * (size_t)n;
+  a.weight = cs.d_dcin.p;
   a.nu = nu;
   a.rows_per_block = nemo::dclass_rows_per_block(V0, nu);
-  a.hash = reinterpret_cast<uint64_t *>(cs.d_dcacc);
-  a.pop = cs.d_dcacc + 4 * (size_t)cs.dc_cap;
-  a.support = cs.d_dcacc + 5 * (size_t)cs.dc_cap;
-  nemo::launch_to_host(cs.d_dcin, c->h_dcin.p, 4ull * nu, s);  // pinned -> device by a copy kernel
-  nemo::launch_zero(cs.d_dcacc, 4 * (5 * (uint64_t)cs.dc_cap + V0), s);
+  a.hash = reinterpret_cast<uint64_t *>(cs.d_dcacc.p);
+  a.pop = cs.d_dcacc.p + 4 * (size_t)cs.dc_cap;
+  a.support = cs.d_dcacc.p + 5 * (size_t)cs.dc_cap;
+  nemo::launch_to_host(cs.d_dcin.p, c->h_dcin.p, 4ull * nu, s);  // pinned -> device by a copy kernel
+  nemo::launch_zero(cs.d_dcacc.p, 4 * (5 * (uint64_t)cs.dc_cap + V0), s);
   // algorithmic bytes: every distinct row once, 20 bytes per source and the support written
   if ((rc = timed_on(c, s, "k_dclass", (double)nu * V0 + 24.0 * nu + 4.0 * V0, 0,
                      [&] { nemo::launch_dclass_hash(a, s); })))
@@ -448,12 +424,12 @@ int nemo_diff_classes(nemo_ctx *c) {
     const uint32_t np = (uint32_t)(pairs.size() / 2);  // < nu
     if (np) {
       memcpy(c->h_dcin.p, pairs.data(), pairs.size() * 4);
-      nemo::launch_to_host(cs.d_dcin, c->h_dcin.p, 8ull * np, s);
+      nemo::launch_to_host(cs.d_dcin.p, c->h_dcin.p, 8ull * np, s);
       // each verified row and its candidate once more
       if ((rc = timed_on(c, s, "k_dclass", 2.0 * np * V0 + 9.0 * np, 0,
-                         [&] { nemo::launch_dclass_cmp(a, cs.d_dcin, np, cs.d_dcv, s); })))
+                         [&] { nemo::launch_dclass_cmp(a, cs.d_dcin.p, np, cs.d_dcv.p, s); })))
         return rc;
-      nemo::launch_to_host(h_v, cs.d_dcv, np, s);
+      nemo::launch_to_host(h_v, cs.d_dcv.p, np, s);
       HIPCHK(c, hipEventRecord(c->ev_dclass, s));
       HIPCHK(c, hipEventSynchronize(c->ev_dclass));
     }
@@ -537,7 +513,7 @@ static int sdiff_impl(nemo_ctx *c, bool per_pair, const uint32_t *failed_iters, 
     }
     if ((rc = run_index(c, failed_iters[e], &r))) return rc;
     const uint32_t g = 2 * r + 1;
-    const uint64_t V = c->cs.node_off[g + 1] - c->cs.node_off[g], E = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+    const uint64_t V = c->cs.nv(g), E = c->cs.ne(g);
     graph[e] = g;
     off[e + 1] = off[e] + V;
     if (tier_fits(c->cs.dc.t_diff, (uint32_t)std::min<uint64_t>(V, ~0u), (uint32_t)std::min<uint64_t>(E, ~0u), 0)) n_lds++;
@@ -546,80 +522,51 @@ static int sdiff_impl(nemo_ctx *c, bool per_pair, const uint32_t *failed_iters, 
     edges += 3.0 * E;
   }
   const uint64_t total = off[n_failed];
-  const bool grow_v = total > c->cs.sd_vcap || !c->cs.d_sdmask, grow_b = n_glob && (total > c->cs.sd_bcap || !c->cs.d_sdbits);
+  CorpusState &cs = c->cs;
   // the pairs call's tables (pairs_host.h): one per distinct `other` run but run 0, whose table the load built
   pairs::Plan plan;
   if (per_pair) {
-    plan = pairs::plan(other.data(), n_failed, c->cs.node_off.data(), c->cs.run0 >= 0 ? 2 * (int64_t)c->cs.run0 + 1 : -1);
+    plan = pairs::plan(other.data(), n_failed, cs.node_off.data(), cs.run0 >= 0 ? (int64_t)cs.g0() : -1);
     if (!plan.ok) return fail(c, NEMO_ERR_LIMIT, "%s: a label table would exceed 2^32 slots", who);
   }
   const size_t n_tabs = plan.tab_graph.size();
-  const bool grow_t = per_pair && (n_failed > c->cs.sd_tcap || !c->cs.d_sdtab);
-  const bool grow_h = plan.words > c->cs.ph_cap;
-  if (n_failed > c->cs.sd_ecap || grow_v || grow_b || grow_t || grow_h) {
+  // per-entry buffers in whole 64-entry chunks; the ragged ones and the table region exactly the largest request so far
+  const uint64_t ecap = (n_failed + 63) & ~(uint64_t)63;
+  const bool grow_e = ecap > cs.d_sdgraph.cap || !cs.d_sdoff.p, grow_v = total > cs.d_sdmask.cap || !cs.d_sdrows.p;
+  if (grow_e || grow_v || (per_pair && 2 * ecap > cs.d_sdtab.cap) || plan.words > cs.d_phreg.cap || (n_glob && !cs.d_sdbits.p)) {
     // an earlier symmetric / pairs call or its pull may still use the buffers
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (grow_t) {  // entry descriptors, then table descriptors (at most one per entry)
-      dfree(c, c->cs.d_sdtab);
-      c->cs.d_sdtab = nullptr;
-      c->cs.sd_tcap = 0;
-      const uint64_t cap = (n_failed + 63) & ~(uint64_t)63;
-      if ((rc = dalloc(c, &c->cs.d_sdtab, 2 * cap))) return rc;
-      c->cs.sd_tcap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-    }
-    if (grow_h) {  // the table region, grown like d_sdmask: exactly the largest request so far
-      dfree(c, c->cs.d_phreg);
-      c->cs.d_phreg = nullptr;
-      c->cs.ph_cap = 0;
-      if ((rc = dalloc(c, &c->cs.d_phreg, plan.words))) return rc;
-      c->cs.ph_cap = plan.words;
-    }
-    if (n_failed > c->cs.sd_ecap) {
-      dfree(c, c->cs.d_sdgraph);
-      dfree(c, c->cs.d_sdoff);
-      c->cs.d_sdgraph = nullptr;
-      c->cs.d_sdoff = nullptr;
-      c->cs.sd_ecap = 0;
-      const uint64_t cap = (n_failed + 63) & ~(uint64_t)63;
-      if ((rc = dalloc(c, &c->cs.d_sdgraph, cap))) return rc;
-      if ((rc = dalloc(c, &c->cs.d_sdoff, cap + 1))) return rc;
-      c->cs.sd_ecap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+    // entry descriptors, then table descriptors (at most one per entry)
+    if (per_pair && (rc = cs.d_sdtab.grow(c, 2 * ecap))) return rc;
+    if (plan.words && (rc = cs.d_phreg.grow(c, plan.words))) return rc;
+    if (grow_e) {
+      cs.d_sdgraph.release(c), cs.d_sdoff.release(c);
+      if ((rc = cs.d_sdgraph.grow(c, ecap)) || (rc = cs.d_sdoff.grow(c, ecap + 1))) return rc;
     }
     if (grow_v) {
-      for (void *q : {(void *)c->cs.d_sdmask, (void *)c->cs.d_sddepth, (void *)c->cs.d_sdrows, (void *)c->cs.d_sdbits}) dfree(c, q);
-      c->cs.d_sdmask = c->cs.d_sdbits = nullptr;
-      c->cs.d_sddepth = nullptr;
-      c->cs.d_sdrows = nullptr;
-      c->cs.sd_vcap = c->cs.sd_bcap = 0;
-      if ((rc = dalloc(c, &c->cs.d_sdmask, total))) return rc;
-      if ((rc = dalloc(c, &c->cs.d_sddepth, total))) return rc;
+      cs.d_sdmask.release(c), cs.d_sddepth.release(c), cs.d_sdrows.release(c), cs.d_sdbits.release(c);
       // a row per S rule at most, and the rules of all entries are at most their nodes: no overflow
-      if ((rc = dalloc(c, &c->cs.d_sdrows, 2 * total + 2))) return rc;
-      c->cs.sd_vcap = total;
+      if ((rc = cs.d_sdmask.grow(c, total)) || (rc = cs.d_sddepth.grow(c, total)) || (rc = cs.d_sdrows.grow(c, 2 * total + 2)))
+        return rc;
     }
-    if (grow_b || (n_glob && grow_v)) {  // node bits of the global tier only
-      dfree(c, c->cs.d_sdbits);
-      c->cs.d_sdbits = nullptr;
-      c->cs.sd_bcap = 0;
-      if ((rc = dalloc(c, &c->cs.d_sdbits, c->cs.sd_vcap))) return rc;
-      c->cs.sd_bcap = c->cs.sd_vcap;
-    }
+    // node bits of the global tier only, as many as d_sdmask holds (live ones were allocated at that size)
+    if (n_glob && (rc = cs.d_sdbits.grow(c, cs.d_sdmask.cap))) return rc;
   }
-  if (!c->cs.d_sdn && (rc = dalloc(c, &c->cs.d_sdn, 1))) return rc;
+  if ((rc = cs.d_sdn.grow(c, 1))) return rc;
   hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->cs.d_sdgraph, graph.data(), n_failed * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->cs.d_sdoff, off.data(), (n_failed + 1) * 8, hipMemcpyHostToDevice, s));
-  nemo::launch_zero(c->cs.d_sdn, 4, s);
+  HIPCHK(c, hipMemcpyAsync(c->cs.d_sdgraph.p, graph.data(), n_failed * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->cs.d_sdoff.p, off.data(), (n_failed + 1) * 8, hipMemcpyHostToDevice, s));
+  nemo::launch_zero(c->cs.d_sdn.p, 4, s);
   std::vector<nemo::LabTab> tabs;  // (kept in sd_tabs below, as graph and off are: the uploads read them)
   if (per_pair) {
     // [entries] the table each entry probes, then [tables] the tables k_lab_hash fills
     tabs.resize(n_failed + n_tabs);
     for (size_t t = 0; t < n_tabs; t++)
-      tabs[n_failed + t] = {c->cs.d_phreg + plan.tab_off[t], plan.tab_mask[t], plan.tab_graph[t]};
+      tabs[n_failed + t] = {c->cs.d_phreg.p + plan.tab_off[t], plan.tab_mask[t], plan.tab_graph[t]};
     for (size_t e = 0; e < n_failed; e++)
       tabs[e] = plan.entry_tab[e] == PAIRS_SHARED ? nemo::LabTab{c->cs.d_r0hkey, c->cs.r0hmask, other[e]}
                                                    : tabs[n_failed + plan.entry_tab[e]];
-    HIPCHK(c, hipMemcpyAsync(c->cs.d_sdtab, tabs.data(), tabs.size() * sizeof(nemo::LabTab), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->cs.d_sdtab.p, tabs.data(), tabs.size() * sizeof(nemo::LabTab), hipMemcpyHostToDevice, s));
     // tables of at most pair_hash_lds_max slots are built in LDS; the launch's LDS is the largest of them
     const uint32_t lds_max = c->opt.pair_hash_lds_max;
     uint32_t lds_slots = 0;
@@ -627,21 +574,21 @@ static int sdiff_impl(nemo_ctx *c, bool per_pair, const uint32_t *failed_iters, 
       if (plan.tab_mask[t] < lds_max) lds_slots = std::max(lds_slots, plan.tab_mask[t] + 1u);
     // algorithmic bytes: node word + label of every hashed graph, and the tables written
     if (n_tabs && (rc = timed(c, "k_lab_hash", 8.0 * (double)plan.nodes + 4.0 * (double)plan.words, 0, [&] {
-           nemo::launch_lab_hash(c->cs.dc, c->cs.d_sdtab + n_failed, (uint32_t)n_tabs, lds_max, lds_slots, s);
+           nemo::launch_lab_hash(c->cs.dc, c->cs.d_sdtab.p + n_failed, (uint32_t)n_tabs, lds_max, lds_slots, s);
          })))
       return rc;
   }
   nemo::SdiffArgs a{};
-  a.graph = c->cs.d_sdgraph;
-  a.off = c->cs.d_sdoff;
+  a.graph = c->cs.d_sdgraph.p;
+  a.off = c->cs.d_sdoff.p;
   a.r0hkey = c->cs.d_r0hkey;
   a.r0hmask = c->cs.r0hmask;
-  a.tabs = per_pair ? c->cs.d_sdtab : nullptr;
-  a.bits = c->cs.d_sdbits;
-  a.depth = c->cs.d_sddepth;
-  a.mask = c->cs.d_sdmask;
-  a.rows = c->cs.d_sdrows;
-  a.n_rows = c->cs.d_sdn;
+  a.tabs = per_pair ? c->cs.d_sdtab.p : nullptr;
+  a.bits = c->cs.d_sdbits.p;
+  a.depth = c->cs.d_sddepth.p;
+  a.mask = c->cs.d_sdmask.p;
+  a.rows = c->cs.d_sdrows.p;
+  a.n_rows = c->cs.d_sdn.p;
   if ((rc = timed(c, "k_sdiff", bytes, edges,
                   [&] { nemo::launch_sdiff(c->cs.dc, a, (uint32_t)n_failed, n_lds, n_glob, s); })))
     return rc;
@@ -671,7 +618,7 @@ int nemo_fetch_sdiff_masks(nemo_ctx *c, uint64_t *off, uint8_t *out, uint64_t ca
   if (cap < total) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   if (total) {
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->cs.d_sdmask, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->cs.d_sdmask.p, total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return NEMO_OK;
@@ -683,7 +630,7 @@ int nemo_fetch_surplus(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
   uint32_t n = 0;
   if (c->cs.n_sentries) {
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(&n, c->cs.d_sdn, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&n, c->cs.d_sdn.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   if (n_out) *n_out = n;
@@ -691,7 +638,7 @@ int nemo_fetch_surplus(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   if (!n) return NEMO_OK;
   std::vector<uint32_t> rows(2 * (size_t)n);
-  HIPCHK(c, hipMemcpyAsync(rows.data(), c->cs.d_sdrows, 8ull * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(rows.data(), c->cs.d_sdrows.p, 8ull * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   sort_rows<2>(rows.data(), n);  // the device emits in any order: by (entry, rule)
   for (uint32_t k = 0; k < n; k++) {

@@ -5,9 +5,9 @@ extern "C" {
 
 static int pull_launch(nemo_ctx *c) {
   nemo::PullArgs &a = c->cs.pull_args;
-  a.src = c->cs.d_psrc;
-  a.dst = c->cs.d_pdst;
-  a.cap = c->cs.pull_cap;
+  a.src = c->cs.d_psrc.p;
+  a.dst = c->cs.d_pdst.p;
+  a.cap = c->cs.d_pdst.cap;
   const uint32_t slots = c->cs.pull_dslots;
   hipStream_t s = c->stream;
   // the simplified pull reads what nemo_simplify left (graphs, flags, chains): on `aux`, behind
@@ -21,19 +21,19 @@ static int pull_launch(nemo_ctx *c) {
   double V = (double)c->cs.V, E = (double)c->cs.E;
   if (a.which == 2) {
     V = (double)slots * (double)a.mask_stride;
-    E = (double)slots * (double)(c->cs.edge_off[a.g0 + 1] - c->cs.edge_off[a.g0]);
+    E = (double)slots * (double)c->cs.ne(a.g0);
   }
-  nemo::launch_zero(c->cs.d_pcur, sizeof(unsigned long long), s);
+  nemo::launch_zero(c->cs.d_pcur.p, sizeof(unsigned long long), s);
   // algorithmic bytes: the read side (node flags, both row pointers, columns, masks)
   uint32_t rest = c->cs.pull_rest;
   if (a.which == 2) {
-    const uint64_t v0 = c->cs.node_off[a.g0 + 1] - c->cs.node_off[a.g0], e0 = c->cs.edge_off[a.g0 + 1] - c->cs.edge_off[a.g0];
+    const uint64_t v0 = c->cs.nv(a.g0), e0 = c->cs.ne(a.g0);
     rest = !tier_fits(c->cs.dc.t_pull, (uint32_t)std::min<uint64_t>(v0, ~0u), (uint32_t)std::min<uint64_t>(e0, ~0u), 0);
   } else if (a.which == 3) {  // every entry has its own graph
     V = E = 0;
     rest = 0;
     for (uint32_t g : c->cs.sd_graph) {
-      const uint64_t v = c->cs.node_off[g + 1] - c->cs.node_off[g], e = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+      const uint64_t v = c->cs.nv(g), e = c->cs.ne(g);
       V += (double)v;
       E += (double)e;
       rest += !tier_fits(c->cs.dc.t_pull, (uint32_t)std::min<uint64_t>(v, ~0u), (uint32_t)std::min<uint64_t>(e, ~0u), 0);
@@ -42,9 +42,9 @@ static int pull_launch(nemo_ctx *c) {
   int rc = timed_on(c, s, "k_pull", 4 * E + 13 * V, E, [&] { nemo::launch_pull(c->cs.dc, a, slots, rest, s); });
   if (rc) return rc;
   nemo::HostCopies hc;
-  hc.add(c->h_pull.off.p, c->cs.d_poff, slots * 8ull);
-  hc.add(c->h_pull.cnt.p, c->cs.d_pcnt, slots * 4ull);
-  hc.add(c->h_pull.cur.p, c->cs.d_pcur, sizeof(unsigned long long));
+  hc.add(c->h_pull.off.p, c->cs.d_poff.p, slots * 8ull);
+  hc.add(c->h_pull.cnt.p, c->cs.d_pcnt.p, slots * 4ull);
+  hc.add(c->h_pull.cur.p, c->cs.d_pcur.p, sizeof(unsigned long long));
   nemo::launch_to_host_multi(hc, s);
   HIPCHK(c, hipEventRecord(c->ev_pull, s));
   if (on_aux) {
@@ -57,17 +57,11 @@ static int pull_launch(nemo_ctx *c) {
 }
 
 static int pull_grow(nemo_ctx *c, uint64_t total) {
-  if (total <= c->cs.pull_cap) return NEMO_OK;
+  if (total <= c->cs.d_pdst.cap) return NEMO_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dfree(c, c->cs.d_psrc);
-  dfree(c, c->cs.d_pdst);
-  c->cs.d_psrc = c->cs.d_pdst = nullptr;
-  c->cs.pull_cap = 0;
-  int rc;
-  if ((rc = dalloc(c, &c->cs.d_psrc, total))) return rc;
-  if ((rc = dalloc(c, &c->cs.d_pdst, total))) return rc;
-  c->cs.pull_cap = total;
-  return NEMO_OK;
+  c->cs.d_psrc.release(c), c->cs.d_pdst.release(c);
+  if (int rc = c->cs.d_psrc.grow(c, total)) return rc;
+  return c->cs.d_pdst.grow(c, total);
 }
 
 // Wait for the last pull's slot table; re-run it once if its regions overran the capacity.
@@ -75,7 +69,7 @@ static int pull_sync(nemo_ctx *c) {
   if (c->cs.pull_synced) return NEMO_OK;
   HIPCHK(c, hipEventSynchronize(c->ev_pull));
   const uint64_t total = *c->h_pull.cur.p;
-  if (total > c->cs.pull_cap) {
+  if (total > c->cs.d_pdst.cap) {
     int rc = pull_grow(c, total);
     if (!rc) rc = pull_launch(c);
     if (rc) return rc;
@@ -109,7 +103,8 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
   // only when they are about to be reallocated (a pull queued behind another on the same
   // stream overwrites the device tables in order; the host reads them in pull_sync after the
   // last pull's event)
-  if (!c->cs.pull_synced && (slots + 1 > c->cs.pull_slot_cap || (uint64_t)slots + 1 > c->h_pull.cap()))
+  const bool grow_slots = (uint64_t)slots + 1 > c->cs.d_pcnt.cap || !c->cs.d_poff.p;
+  if (!c->cs.pull_synced && (grow_slots || (uint64_t)slots + 1 > c->h_pull.cap()))
     HIPCHK(c, hipEventSynchronize(c->ev_pull));
   c->cs.pull_synced = true;
   if (which == 2 && (rc = join_aux(c))) return rc;  // the D masks
@@ -118,15 +113,10 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
   const bool share = which == 2 && c->cs.n_uniq < c->cs.n_entries;
   const uint32_t dslots = share ? c->cs.n_uniq : slots;
   if ((rc = ensure_event(c, &c->ev_pull))) return rc;
-  if (!c->cs.d_pcur && (rc = dalloc(c, &c->cs.d_pcur, 1))) return rc;
-  if (slots + 1 > c->cs.pull_slot_cap) {
-    dfree(c, c->cs.d_pcnt);
-    dfree(c, c->cs.d_poff);
-    c->cs.d_pcnt = nullptr;
-    c->cs.d_poff = nullptr;
-    if ((rc = dalloc(c, &c->cs.d_pcnt, (size_t)slots + 1))) return rc;
-    if ((rc = dalloc(c, &c->cs.d_poff, (size_t)slots + 1))) return rc;
-    c->cs.pull_slot_cap = slots + 1;
+  if ((rc = c->cs.d_pcur.grow(c, 1))) return rc;
+  if (grow_slots) {
+    c->cs.d_pcnt.release(c), c->cs.d_poff.release(c);
+    if ((rc = c->cs.d_pcnt.grow(c, (uint64_t)slots + 1)) || (rc = c->cs.d_poff.grow(c, (uint64_t)slots + 1))) return rc;
   }
   if ((rc = c->h_pull.grow(c, (uint64_t)slots + 1))) return rc;
   c->cs.pull_which = which;
@@ -137,52 +127,46 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
   if (slots == 0) return NEMO_OK;
   nemo::PullArgs a{};
   a.which = (uint32_t)which;
-  const uint32_t g0 = c->cs.run0 >= 0 ? 2 * c->cs.run0 + 1 : 0;
-  a.g0 = g0;
+  a.g0 = c->cs.run0 >= 0 ? c->cs.g0() : 0;
   uint64_t cap;
   if (which == 2) {
-    a.mask = c->cs.d_dmask;
-    a.mask_stride = c->cs.node_off[g0 + 1] - c->cs.node_off[g0];
-    a.mask_row = share ? c->cs.d_dsrc + 2 * c->cs.n_entries : nullptr;  // diffprov's representative entries
-    cap = (uint64_t)dslots * (c->cs.edge_off[g0 + 1] - c->cs.edge_off[g0]);  // D is an induced subgraph of g0
+    a.mask = c->cs.d_dmask.p;
+    a.mask_stride = c->cs.V0();
+    a.mask_row = share ? c->cs.d_dsrc.p + 2 * c->cs.n_entries : nullptr;  // diffprov's representative entries
+    cap = (uint64_t)dslots * c->cs.E0();  // D is an induced subgraph of g0
   } else if (which == 3) {
     // slot = entry, graph = the entry's failed post graph, liveness = its S mask (ragged)
-    a.slot_g = c->cs.d_sdgraph;
-    a.mask = c->cs.d_sdmask;
-    a.mask_off = c->cs.d_sdoff;
+    a.slot_g = c->cs.d_sdgraph.p;
+    a.mask = c->cs.d_sdmask.p;
+    a.mask_off = c->cs.d_sdoff.p;
     cap = 0;  // S is an induced subgraph of the entry's graph
-    for (uint32_t g : c->cs.sd_graph) cap += c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+    for (uint32_t g : c->cs.sd_graph) cap += c->cs.ne(g);
   } else if (which == 0) {
     cap = c->cs.E;  // every edge
   } else {
     // kept edges (<= E) + collapsed edges; a pull past the estimate re-runs on fetch
     cap = std::max<uint64_t>(2 * c->cs.E + 1024, c->cs.pull_hint[1] + c->cs.pull_hint[1] / 4);
   }
-  a.cnt = c->cs.d_pcnt;
-  a.off = c->cs.d_poff;
-  a.cursor = c->cs.d_pcur;
+  a.cnt = c->cs.d_pcnt.p;
+  a.off = c->cs.d_poff.p;
+  a.cursor = c->cs.d_pcur.p;
   // big graphs' chunk table (k_diff.hip MWP_CH = 4096 nodes or chains per chunk)
   a.ccnt = nullptr;
   a.maxck = 0;
-  const uint64_t vg0 = c->cs.node_off[g0 + 1] - c->cs.node_off[g0];
-  uint32_t rows = which == 2 ? (vg0 >= NEMO_CSR_BIG ? dslots : 0u) : c->cs.dc.n_big;
+  uint32_t rows = which == 2 ? (c->cs.V0() >= NEMO_CSR_BIG ? dslots : 0u) : c->cs.dc.n_big;
   if (which == 3) {  // a chunk-table row per entry as soon as one entry's graph is big
     rows = 0;
     for (uint32_t g : c->cs.sd_graph)
-      if (c->cs.node_off[g + 1] - c->cs.node_off[g] >= NEMO_CSR_BIG) rows = dslots;
+      if (c->cs.nv(g) >= NEMO_CSR_BIG) rows = dslots;
   }
   if (rows) {
     a.maxck = (uint32_t)(2 * ((c->cs.bigVmax + 4095) / 4096));
     const size_t need = (size_t)rows * a.maxck;
-    if (need > c->cs.pull_ck_cap) {
+    if (need > c->cs.d_pck.cap) {
       HIPCHK(c, hipStreamSynchronize(c->stream));  // a previous pull may still use the chunk table
-      dfree(c, c->cs.d_pck);
-      c->cs.d_pck = nullptr;
-      c->cs.pull_ck_cap = 0;
-      if ((rc = dalloc(c, &c->cs.d_pck, need))) return rc;
-      c->cs.pull_ck_cap = need;
+      if ((rc = c->cs.d_pck.grow(c, need))) return rc;
     }
-    a.ccnt = c->cs.d_pck;
+    a.ccnt = c->cs.d_pck.p;
   }
   c->cs.pull_args = a;
   if ((rc = pull_grow(c, std::max<uint64_t>(cap, 1)))) return rc;
@@ -209,8 +193,8 @@ int nemo_fetch_pulled(nemo_ctx *c, uint32_t slot, uint32_t *src, uint32_t *dst, 
   if (!src && !dst) return NEMO_OK;
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   if (n) {
-    if (src) HIPCHK(c, hipMemcpyAsync(src, c->cs.d_psrc + a, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (dst) HIPCHK(c, hipMemcpyAsync(dst, c->cs.d_pdst + a, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (src) HIPCHK(c, hipMemcpyAsync(src, c->cs.d_psrc.p + a, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (dst) HIPCHK(c, hipMemcpyAsync(dst, c->cs.d_pdst.p + a, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return NEMO_OK;
@@ -231,8 +215,8 @@ int nemo_fetch_pulled_all(nemo_ctx *c, uint64_t *off, uint32_t *cnt, uint32_t *s
   if (!src && !dst) return NEMO_OK;
   if (cap < used) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   if (used) {
-    if (src) HIPCHK(c, hipMemcpyAsync(src, c->cs.d_psrc, used * 4, hipMemcpyDeviceToHost, c->stream));
-    if (dst) HIPCHK(c, hipMemcpyAsync(dst, c->cs.d_pdst, used * 4, hipMemcpyDeviceToHost, c->stream));
+    if (src) HIPCHK(c, hipMemcpyAsync(src, c->cs.d_psrc.p, used * 4, hipMemcpyDeviceToHost, c->stream));
+    if (dst) HIPCHK(c, hipMemcpyAsync(dst, c->cs.d_pdst.p, used * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return NEMO_OK;

@@ -14,25 +14,25 @@ int nemo_triggers(nemo_ctx *c) {
   c->cs.trig_pending = false;
   if (c->cs.run0 < 0) return NEMO_OK;
   int rc;
-  if (!c->cs.d_tcounts && (rc = dalloc(c, &c->cs.d_tcounts, 3))) return rc;
+  if ((rc = c->cs.d_tcounts.grow(c, 3))) return rc;
   if ((rc = c->h_tcounts.grow(c, 4))) return rc;
   if ((rc = ensure_event(c, &c->ev_trig))) return rc;
   nemo::TrigArgs a{};
   a.g_pre = 2 * c->cs.run0;
-  a.g_post = 2 * c->cs.run0 + 1;
-  a.counts = c->cs.d_tcounts;
+  a.g_post = c->cs.g0();
+  a.counts = c->cs.d_tcounts.p;
   a.pre = c->cs.d_tpre;
   a.post = c->cs.d_tpost;
   a.async_rules = c->cs.d_tasync;
   hipStream_t s = c->stream;
-  nemo::launch_zero(c->cs.d_tcounts, 12, s);
+  nemo::launch_zero(c->cs.d_tcounts.p, 12, s);
   rc = timed(c, "k_triggers", 0, 0, [&] { nemo::launch_triggers(c->cs.dc, a, 1, s); });
   if (rc) return rc;
   if ((rc = c->h_tpre.grow(c, 3 * c->cs.tcap[0] + 3))) return rc;
   if ((rc = c->h_tpost.grow(c, 2 * c->cs.tcap[1] + 2))) return rc;
   if ((rc = c->h_tasync.grow(c, c->cs.tcap[2] + 1))) return rc;
   nemo::HostCopies hc;
-  hc.add(c->h_tcounts.p, c->cs.d_tcounts, 12);
+  hc.add(c->h_tcounts.p, c->cs.d_tcounts.p, 12);
   hc.add(c->h_tpre.p, c->cs.d_tpre, 12 * c->cs.tcap[0]);
   hc.add(c->h_tpost.p, c->cs.d_tpost, 8 * c->cs.tcap[1]);
   hc.add(c->h_tasync.p, c->cs.d_tasync, 4 * c->cs.tcap[2]);
@@ -104,25 +104,20 @@ int nemo_fetch_chains(nemo_ctx *c, nemo_chain *out, uint64_t cap, uint64_t *n_ou
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   hipStream_t s = c->stream;
-  if (!c->cs.d_choff && (rc = dalloc(c, &c->cs.d_choff, (size_t)c->cs.G + 1))) return rc;
-  rc = timed(c, "k_chain_gather", 0, 0, [&] { nemo::launch_chain_gather(c->cs.dc, c->cs.d_choff, nullptr, s); });
+  if ((rc = c->cs.d_choff.grow(c, (uint64_t)c->cs.G + 1))) return rc;
+  rc = timed(c, "k_chain_gather", 0, 0, [&] { nemo::launch_chain_gather(c->cs.dc, c->cs.d_choff.p, nullptr, s); });
   if (rc) return rc;
   uint64_t n = 0;
-  HIPCHK(c, hipMemcpyAsync(&n, c->cs.d_choff + c->cs.G, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(&n, c->cs.d_choff.p + c->cs.G, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   if (n_out) *n_out = n;
   if (!out) return NEMO_OK;
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
-  if (n > c->cs.chout_cap) {
-    dfree(c, c->cs.d_chout);
-    c->cs.d_chout = nullptr;
-    if ((rc = dalloc(c, &c->cs.d_chout, 5 * n))) return rc;
-    c->cs.chout_cap = n;
-  }
-  rc = timed(c, "k_chain_gather", 0, 0, [&] { nemo::launch_chain_gather(c->cs.dc, c->cs.d_choff, c->cs.d_chout, s); });
+  if (5 * n > c->cs.d_chout.cap && (rc = c->cs.d_chout.grow(c, 5 * n))) return rc;
+  rc = timed(c, "k_chain_gather", 0, 0, [&] { nemo::launch_chain_gather(c->cs.dc, c->cs.d_choff.p, c->cs.d_chout.p, s); });
   if (rc) return rc;
   static_assert(sizeof(nemo_chain) == 20, "nemo_chain layout");
-  if (n) HIPCHK(c, hipMemcpyAsync(out, c->cs.d_chout, n * 20, hipMemcpyDeviceToHost, s));
+  if (n) HIPCHK(c, hipMemcpyAsync(out, c->cs.d_chout.p, n * 20, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return NEMO_OK;
 }
@@ -147,15 +142,15 @@ static hipError_t stage_copy(nemo_ctx *c, void *dst, const void *src, size_t n) 
 static int stage_state(nemo_ctx *c, hipStream_t s) {
   int rc;
   const uint64_t sbytes = 4 * ((c->cs.V + 15) / 16);  // 2-bit node state
-  if (!c->cs.d_state && (rc = dalloc(c, &c->cs.d_state, sbytes / 4 + 1))) return rc;
+  if ((rc = c->cs.d_state.grow(c, sbytes / 4 + 1))) return rc;
   rc = timed_on(c, s, "k_pack_state", (double)c->cs.V + (double)sbytes, 0,
-                [&] { nemo::launch_pack_state(c->cs.dc.flags, c->cs.d_state, c->cs.V, s); });
+                [&] { nemo::launch_pack_state(c->cs.dc.flags, c->cs.d_state.p, c->cs.V, s); });
   if (rc) return rc;
   if ((rc = c->h_flags.grow(c, sbytes + 16))) return rc;
   if ((rc = ensure_event(c, &c->ev_state))) return rc;
   HIPCHK(c, hipEventRecord(c->ev_state, s));
   HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_state, 0));
-  HIPCHK(c, stage_copy(c, c->h_flags.p, c->cs.d_state, sbytes));
+  HIPCHK(c, stage_copy(c, c->h_flags.p, c->cs.d_state.p, sbytes));
   return NEMO_OK;
 }
 
@@ -165,22 +160,18 @@ static int stage_enqueue(nemo_ctx *c, uint64_t cap) {
   int rc;
   hipStream_t s = c->cs.stage_stream ? c->cs.stage_stream : c->stream;
   const uint64_t pw = c->cs.pairs_wide ? 2 : 1;  // u32 words per pair
-  if (pw * cap > c->cs.d_chht_cap) {
+  if (pw * cap + 2 > c->cs.d_chht.cap) {
     HIPCHK(c, hipStreamSynchronize(s));
-    dfree(c, c->cs.d_chht);
-    c->cs.d_chht = nullptr;
-    c->cs.d_chht_cap = 0;
-    if ((rc = dalloc(c, &c->cs.d_chht, pw * cap + 2))) return rc;
-    c->cs.d_chht_cap = pw * cap + 2;
+    if ((rc = c->cs.d_chht.grow(c, pw * cap + 2))) return rc;
   }
   rc = timed_on(c, s, "k_chain_pairs", 4.0 * pw * (double)cap + 20.0 * c->cs.G, 0,
-                [&] { nemo::launch_chain_pairs(c->cs.dc, c->cs.d_choff, c->cs.d_chht, cap, c->cs.pairs_wide ? 1 : 0, s); });
+                [&] { nemo::launch_chain_pairs(c->cs.dc, c->cs.d_choff.p, c->cs.d_chht.p, cap, c->cs.pairs_wide ? 1 : 0, s); });
   if (rc) return rc;
   if ((rc = c->h_chht.grow(c, pw * cap + 2))) return rc;
-  nemo::launch_to_host(c->h_choff.p, c->cs.d_choff, ((size_t)c->cs.G + 1) * 8, s);
+  nemo::launch_to_host(c->h_choff.p, c->cs.d_choff.p, ((size_t)c->cs.G + 1) * 8, s);
   HIPCHK(c, hipEventRecord(c->ev_ready, s));
   HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_ready, 0));
-  HIPCHK(c, stage_copy(c, c->h_chht.p, c->cs.d_chht, pw * cap * 4));
+  HIPCHK(c, stage_copy(c, c->h_chht.p, c->cs.d_chht.p, pw * cap * 4));
   HIPCHK(c, hipEventRecord(c->ev_copied, c->copy));
   c->cs.staged_cap = cap;
   return NEMO_OK;
@@ -210,7 +201,7 @@ int nemo_stage_simplified(nemo_ctx *c) {
   if ((rc = ensure_event(c, &c->ev_ready)) || (rc = ensure_event(c, &c->ev_copied))) return rc;
   if (c->cs.staged) HIPCHK(c, hipEventSynchronize(c->ev_copied));  // host buffers are reused
   c->cs.staged = false;
-  if (!c->cs.d_choff && (rc = dalloc(c, &c->cs.d_choff, (size_t)c->cs.G + 1))) return rc;
+  if ((rc = c->cs.d_choff.grow(c, (uint64_t)c->cs.G + 1))) return rc;
   if ((rc = c->h_choff.grow(c, (uint64_t)c->cs.G + 1))) return rc;
   if (c->opt.stage_on_aux) {  // read-only on the analysis: `stream` goes on to the triggers and pulls
     if (!c->aux) HIPCHK(c, hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
@@ -230,14 +221,14 @@ int nemo_stage_simplified(nemo_ctx *c) {
     return rc;
   }
   c->cs.stage_stream = s;
-  rc = timed_on(c, s, "k_chain_gather", 0, 0, [&] { nemo::launch_chain_gather(c->cs.dc, c->cs.d_choff, nullptr, s); });
+  rc = timed_on(c, s, "k_chain_gather", 0, 0, [&] { nemo::launch_chain_gather(c->cs.dc, c->cs.d_choff.p, nullptr, s); });
   if (rc) return rc;
   // the pair count is only known on the device: stage at the last count seen
   // (no host round trip); nemo_simplified_view re-stages if it was too small
   uint64_t cap = c->cs.chht_hint;
   if (!cap) {
     if ((rc = ensure_event(c, &c->ev_misc))) return rc;
-    nemo::launch_to_host(c->h_choff.p, c->cs.d_choff, ((size_t)c->cs.G + 1) * 8, s);
+    nemo::launch_to_host(c->h_choff.p, c->cs.d_choff.p, ((size_t)c->cs.G + 1) * 8, s);
     HIPCHK(c, hipEventRecord(c->ev_misc, s));
     HIPCHK(c, hipEventSynchronize(c->ev_misc));
     cap = c->h_choff.p[c->cs.G];

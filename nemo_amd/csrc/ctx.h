@@ -33,6 +33,9 @@ struct PendingEv {
 };
 
 static int fail(nemo_ctx *c, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+template <class T>
+static int dalloc(nemo_ctx *c, T **p, size_t n);
+static inline void dfree(nemo_ctx *c, void *p);
 
 #define HIPCHK(c, x)                                                                               \
   do {                                                                                             \
@@ -75,6 +78,41 @@ struct PullHost {
   }
 };
 
+// A device buffer sized per call (the diff, symmetric / pair diff, failure classes, pulls, chain gather and
+// stage buffers): grow-only, the device twin of Pinned.  The block stays owned by nemo_ctx::allocs and the
+// block cache, so there is no destructor and CorpusState{} is "no buffers".  A failed grow leaves {nullptr, 0}.
+// Buffers that grow together are released together and then allocated in a fixed order (the dalloc / dfree
+// sequence decides which cached block an array gets at the next load); the site tests the first one's capacity
+// and the pointer of the one allocated last, which is set only when the whole group is.
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  uint64_t cap = 0;  // elements
+  int grow(nemo_ctx *c, uint64_t n) {
+    if (p && n <= cap) return NEMO_OK;
+    release(c);
+    if (int rc = dalloc(c, &p, n)) return rc;
+    cap = n;
+    return NEMO_OK;
+  }
+  void release(nemo_ctx *c) {
+    dfree(c, p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// Graph g = nodes [node_off[g], node_off[g + 1]), edges likewise; run r's graphs are 2r (pre) and 2r + 1 (post).
+struct GraphSizes {
+  std::vector<uint64_t> node_off, edge_off;
+  int32_t run0 = -1;
+  uint64_t nv(uint32_t g) const { return node_off[g + 1] - node_off[g]; }
+  uint64_t ne(uint32_t g) const { return edge_off[g + 1] - edge_off[g]; }
+  uint32_t g0() const { return 2 * (uint32_t)run0 + 1; }  // run 0's post graph: only with run0 >= 0
+  uint64_t V0() const { return run0 >= 0 ? nv(g0()) : 0; }
+  uint64_t E0() const { return run0 >= 0 ? ne(g0()) : 0; }
+};
+
 // nemo_set_option's values.  They outlive loads; some take effect at the next load only.
 struct Options {
   uint32_t hcap_limit = 0xFFFFFFFFu, comp_limit = 0xFFFFFFFFu, build_limit = 0xFFFFFFFFu;
@@ -111,16 +149,14 @@ struct Options {
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
 // default initialiser is its value with no corpus loaded.  Device pointers point into nemo_ctx::allocs.
-struct CorpusState {
-  // host view
+struct CorpusState : GraphSizes {
+  // host view (the graph offsets and run0 are GraphSizes')
   bool loaded = false, marked = false, simplified = false, protos_done = false;
   uint32_t n_runs = 0, G = 0, T = 0, W = 0, table_pre = 0, table_post = 0;
   uint64_t V = 0, E = 0;
   std::vector<uint32_t> iteration;
   std::vector<uint8_t> owned;
-  std::vector<uint64_t> node_off, edge_off;
   std::unordered_map<uint32_t, uint32_t> it2run;
-  int32_t run0 = -1;
   bool has_rank = false;
   bool pairs_wide = false;           // some graph has >= 65536 nodes: u32 chain pairs
   double tierV = 0, tierE = 0;       // nodes / edges of the graphs within the tier's V/E caps
@@ -157,20 +193,21 @@ struct CorpusState {
   uint32_t *d_gd_pairs = nullptr;    // [2 gd_npairs] (dup, rep) sorted by rep
   double gd_bytes[3] = {0, 0, 0};    // what a replicate pass writes per phase at most (timing table)
 
-  // diff
-  uint32_t n_entries = 0, diff_cap = 0, legacy_cap = 0;
+  // diff: per-call buffers in whole 64-entry chunks.  d_dsrc, d_dmask, d_miss grow together; so do the
+  // one-workgroup-per-entry kernels' scratch d_dbits, d_dumask, d_ddepth, d_dtopo
+  uint32_t n_entries = 0;
   uint32_t *d_r0lab = nullptr, *d_r0idx = nullptr, n_r0lab = 0;
   uint32_t *d_r0hkey = nullptr, *d_r0hval = nullptr, r0hmask = 0;
   uint32_t *d_r0dense = nullptr, nlab = 0;  // the dense label table of the multi-entry diff (DxArgs::r0dense)
-  uint32_t *d_dsrc = nullptr, *d_miss = nullptr, *d_nmiss = nullptr;
-  uint8_t *d_dbits = nullptr, *d_dmask = nullptr;
-  int32_t *d_ddepth = nullptr;
-  uint32_t *d_dtopo = nullptr;       // g0 in Kahn order (DiffArgs::tpos ...)
+  DevBuf<uint32_t> d_dsrc, d_miss, d_nmiss;
+  DevBuf<uint8_t> d_dbits, d_dmask;
+  DevBuf<int32_t> d_ddepth;
+  DevBuf<uint32_t> d_dtopo;          // g0 in Kahn order (DiffArgs::tpos ...)
   uint64_t mrows_staged = 0;         // missing rows copied with the D masks
   // entries that share a label source share one computation: n_uniq distinct
   // sources, entry e's result is unique result dmap[e] (d_dmap on the device)
-  uint32_t n_uniq = 0, *d_dmap = nullptr;
-  uint8_t *d_dumask = nullptr;       // [n_uniq * V0] when n_uniq < n_entries
+  uint32_t n_uniq = 0, *d_dmap = nullptr;  // (d_dmap points into d_dsrc)
+  DevBuf<uint8_t> d_dumask;          // [n_uniq * V0] when n_uniq < n_entries
   std::vector<uint32_t> dmap;
   bool aux_pending = false;          // diff kernels queued on `aux` that `stream` has not joined (join_aux)
   // the multi-entry diff (k_dx.hip): g0's Kahn-order relayout, built with the
@@ -181,22 +218,21 @@ struct CorpusState {
   int dx_img_key = -1;               // -1: not built for the current load
   bool dx_ok = false;                // relayout allocated: run 0 present, every row fits a window
   uint32_t g0_maxdeg = 0;
-  uint32_t dx_nu_cap = 0, dx_nch_cap = 0;
-  uint32_t *d_dxpb = nullptr, *d_dxsval = nullptr, *d_dxlpl = nullptr, *d_dxfb = nullptr;
-  uint64_t *d_dxw = nullptr;  // [4][nch][V0] Good / LP, B, D, leaf candidates
+  uint32_t dx_nu_cap = 0;            // sources the five buffers below hold (whole chunks); wflag's offset in d_dxlpl
+  DevBuf<uint32_t> d_dxpb, d_dxsval, d_dxlpl, d_dxfb;
+  DevBuf<uint64_t> d_dxw;  // [4][nch][V0] Good / LP, B, D, leaf candidates
   bool dx_last = false;              // the last diffprov ran the multi-entry kernels
-  uint32_t *d_hlab = nullptr;        // nemo_diffprov_host_labels' set [n, label...]
-  uint64_t hlab_cap = 0;
+  DevBuf<uint32_t> d_hlab;           // nemo_diffprov_host_labels' set [n, label...]
 
   // failure classes (k_dclass.hip): results of the last nemo_diff_classes, void after the next
   // diffprov / rebuild; buffers grow only, per-source sizes in whole 64-source chunks
   bool diff_done = false;            // a diffprov completed on the loaded corpus (n_entries may be 0)
   bool dc_done = false;
   hipStream_t diff_stream = nullptr;  // the stream the last diffprov's kernels went on (`aux` or the context's)
-  uint32_t dc_cap = 0;               // sources the buffers hold
-  uint32_t *d_dcacc = nullptr;       // [4 cap] hashes | [cap] |D| | [V0] support: zeroed, then summed into
-  uint32_t *d_dcin = nullptr;        // [2 cap] the sources' entry counts, then a round's (row, candidate) pairs
-  uint8_t *d_dcv = nullptr;          // [cap] a round's verdicts
+  uint32_t dc_cap = 0;               // sources the buffers hold; the offset of |D| and of the support in d_dcacc
+  DevBuf<uint32_t> d_dcacc;          // [4 cap] hashes | [cap] |D| | [V0] support: zeroed, then summed into
+  DevBuf<uint32_t> d_dcin;           // [2 cap] the sources' entry counts, then a round's (row, candidate) pairs
+  DevBuf<uint8_t> d_dcv;             // [cap] a round's verdicts
   std::vector<uint32_t> dc_class_of;
   std::vector<nemo_diff_class> dc_classes;
   std::vector<dclass::Hash> dc_hash;  // per class: its mask's hash (the node context merges shards by it)
@@ -206,33 +242,36 @@ struct CorpusState {
   // symmetric diff (k_sdiff.hip): all of it the call's own state, so that a symmetric call leaves
   // the results of a previous nemo_diffprov alone and the reverse; buffers grow only
   bool sd_done = false;              // a symmetric call completed on the loaded corpus (n_sentries may be 0)
-  uint32_t n_sentries = 0, sd_ecap = 0;
-  uint64_t sd_vcap = 0, sd_bcap = 0;  // nodes the ragged buffers / the global tier's bits hold
+  uint32_t n_sentries = 0;
   std::vector<uint32_t> sd_graph;    // entry -> its failed post graph
   std::vector<uint64_t> sd_off;      // [n + 1] entry -> first node of its slices
-  uint32_t *d_sdgraph = nullptr, *d_sdrows = nullptr, *d_sdn = nullptr;
-  uint64_t *d_sdoff = nullptr;
-  uint8_t *d_sdmask = nullptr, *d_sdbits = nullptr;
-  int32_t *d_sddepth = nullptr;
+  DevBuf<uint32_t> d_sdgraph;        // per entry, in whole 64-entry chunks; grows with d_sdoff
+  DevBuf<uint64_t> d_sdoff;
+  // the ragged buffers, exactly the largest node total so far: d_sdmask, d_sddepth, d_sdrows grow together;
+  // d_sdbits (the global tier's node bits, as many as d_sdmask) is dropped with them and comes back only
+  // for a call with a global-tier entry
+  DevBuf<uint8_t> d_sdmask, d_sdbits;
+  DevBuf<int32_t> d_sddepth;
+  DevBuf<uint32_t> d_sdrows, d_sdn;
   // nemo_diffprov_pairs (the same state, and): the entries' and the tables' descriptors, and the
   // per-call region k_lab_hash builds the `other` runs' label tables in (pairs_host.h); grow only
-  nemo::LabTab *d_sdtab = nullptr;   // [2 sd_tcap] entry -> its table, then the tables of the call
-  uint32_t sd_tcap = 0;
+  DevBuf<nemo::LabTab> d_sdtab;      // [2 x entries in whole chunks] entry -> its table, then the tables of the call
   std::vector<nemo::LabTab> sd_tabs;  // the last call's upload
-  uint32_t *d_phreg = nullptr;       // [ph_cap] u32 slots
-  uint64_t ph_cap = 0;
+  DevBuf<uint32_t> d_phreg;          // u32 slots, exactly the largest request so far
 
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
-  uint32_t pull_slots = 0, pull_slot_cap = 0;
+  uint32_t pull_slots = 0;
   uint32_t pull_dslots = 0;              // slots computed: diff entries sharing a label source share one
   std::vector<uint32_t> pull_map;        // which 2 with shared slots: entry -> computed slot
-  uint32_t *d_pck = nullptr;          // big graphs' pull chunk table
-  size_t pull_ck_cap = 0;
-  uint32_t *d_pcnt = nullptr, *d_psrc = nullptr, *d_pdst = nullptr;
-  uint64_t *d_poff = nullptr, pull_cap = 0;
-  unsigned long long *d_pcur = nullptr;
+  DevBuf<uint32_t> d_pck;             // big graphs' pull chunk table
+  DevBuf<uint32_t> d_pcnt;            // the slot tables: d_pcnt and d_poff grow together
+  DevBuf<uint64_t> d_poff;
+  // the regions: d_psrc and d_pdst grow together (pull_grow); d_pdst, allocated last, has the pull's
+  // capacity in edges (PullArgs::cap)
+  DevBuf<uint32_t> d_psrc, d_pdst;
+  DevBuf<unsigned long long> d_pcur;
   bool pull_synced = true;
   bool pull_aux_pending = false;      // a pull on `aux` not yet joined by `stream` (guard_staged)
   uint64_t pull_hint[4] = {0, 0, 0, 0};
@@ -241,22 +280,22 @@ struct CorpusState {
   // triggers: outputs sized at load from run 0's degrees (exact bounds), one
   // launch; the row counts come back to pinned memory asynchronously
   bool trig_done = false, trig_pending = false;
-  uint32_t *d_tcounts = nullptr, *d_tpre = nullptr, *d_tpost = nullptr, *d_tasync = nullptr;
+  DevBuf<uint32_t> d_tcounts;
+  uint32_t *d_tpre = nullptr, *d_tpost = nullptr, *d_tasync = nullptr;  // (the load's)
   uint32_t tcounts[3] = {0, 0, 0};
   uint64_t tcap[3] = {0, 0, 0};
 
   // chain gather
-  uint32_t *d_chout = nullptr;
-  uint64_t *d_choff = nullptr, chout_cap = 0;
+  DevBuf<uint32_t> d_chout;  // 5 words per chain
+  DevBuf<uint64_t> d_choff;
 
   // staged simplification results
   bool flags_final = false;  // ev_flags marks the current flags (no flag-rewriting call since)
   hipStream_t stage_stream = nullptr;  // the stream the last stage's hand-over kernels went on
   bool staged = false;
   uint64_t staged_n = 0, staged_cap = 0, chht_hint = 0;
-  uint32_t *d_state = nullptr;  // 2-bit node state (k_pack_state)
-  uint32_t *d_chht = nullptr;
-  uint64_t d_chht_cap = 0;
+  DevBuf<uint32_t> d_state;  // 2-bit node state (k_pack_state)
+  DevBuf<uint32_t> d_chht;   // the staged chain pairs and two words of padding
 };
 
 struct nemo_ctx {
@@ -328,6 +367,9 @@ struct nemo_ctx {
   std::multimap<size_t, void *> cache;
   // NEMO_LOAD_DEBUG: dalloc calls since the load began and a running hash of their sizes in order
   uint64_t dalloc_n = 0, dalloc_hash = 0;
+  // ... and the per-call requests: dalloc / dfree calls since the last load finished, and the same hash over
+  // their sizes in order (release_corpus prints them)
+  uint64_t call_dalloc_n = 0, call_dfree_n = 0, call_hash = 0xCBF29CE484222325ull;
 
   // per-kernel timing
   std::vector<std::string> tgroups;  // nemo_set_timing_groups: the timed groups (empty: all)
@@ -365,6 +407,8 @@ static int dalloc(nemo_ctx *c, T **p, size_t n) {
   const size_t bytes = (n * sizeof(T) + 15) & ~(size_t)15;
   c->dalloc_n++;
   c->dalloc_hash = (c->dalloc_hash ^ bytes) * 0x100000001B3ull;  // the request order decides who gets which cached block
+  c->call_dalloc_n++;
+  c->call_hash = (c->call_hash ^ bytes) * 0x100000001B3ull;
   auto it = c->cache.lower_bound(bytes);  // the smallest cached block that fits, if not much larger
   if (it != c->cache.end() && it->first <= bytes + bytes / 8 + (1u << 20)) {
     q = it->second;
@@ -399,6 +443,9 @@ static inline void dfree(nemo_ctx *c, void *p) {
   if (!p) return;
   auto it = std::find(c->allocs.begin(), c->allocs.end(), p);
   if (it != c->allocs.end()) c->allocs.erase(it);
+  auto b = c->alloc_bytes.find(p);
+  c->call_dfree_n++;
+  c->call_hash = (c->call_hash ^ (b != c->alloc_bytes.end() ? b->second : 0)) * 0x100000001B3ull;
   c->alloc_bytes.erase(p);
   hipFree(p);
 }
@@ -507,7 +554,7 @@ static inline int check_graph_errors(nemo_ctx *c) {
   for (uint32_t g = 0; g < c->cs.G; g++) {
     if (!err[g]) continue;
     const uint32_t it = c->cs.iteration[g / 2];
-    const uint64_t E = c->cs.edge_off[g + 1] - c->cs.edge_off[g];
+    const uint64_t E = c->cs.ne(g);
     if (err[g] == NEMO_ERR_LOAD)
       return fail(c, NEMO_ERR_LOAD,
                   "Run %u: inserted number of edges (%u) does not equal number of antecedent provenance edges (%llu)",

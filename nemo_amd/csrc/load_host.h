@@ -28,8 +28,8 @@ inline int load_validate(nemo_ctx *c, const nemo_corpus *in) {
   s.E = s.edge_off[s.G];
   s.postV = s.postE = 0;
   for (uint32_t g = 1; g < s.G; g += 2) {
-    s.postV += (double)(s.node_off[g + 1] - s.node_off[g]);
-    s.postE += (double)(s.edge_off[g + 1] - s.edge_off[g]);
+    s.postV += (double)s.nv(g);
+    s.postE += (double)s.ne(g);
   }
   s.it2run.clear();
   s.run0 = -1;
@@ -42,13 +42,13 @@ inline int load_validate(nemo_ctx *c, const nemo_corpus *in) {
   for (uint32_t g = 0; g < s.G; g++) {
     if (s.node_off[g + 1] < s.node_off[g] || s.edge_off[g + 1] < s.edge_off[g])
       return fail(c, NEMO_ERR_INVALID, "offsets not monotone at graph %u", g);
-    if (s.node_off[g + 1] - s.node_off[g] >= 0xFFFFFFF0ull || s.edge_off[g + 1] - s.edge_off[g] >= 0xFFFFFFF0ull)
+    if (s.nv(g) >= 0xFFFFFFF0ull || s.ne(g) >= 0xFFFFFFF0ull)
       return fail(c, NEMO_ERR_LIMIT, "graph %u exceeds 2^32 nodes/edges", g);
   }
   if (s.node_off[0] != 0 || s.edge_off[0] != 0) return fail(c, NEMO_ERR_INVALID, "offsets must start at 0");
   s.has_rank = in->id_rank != nullptr;
   s.pairs_wide = false;
-  for (uint32_t g = 0; g < s.G; g++) s.pairs_wide |= s.node_off[g + 1] - s.node_off[g] >= 65536;
+  for (uint32_t g = 0; g < s.G; g++) s.pairs_wide |= s.nv(g) >= 65536;
   return NEMO_OK;
 }
 

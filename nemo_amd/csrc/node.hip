@@ -113,7 +113,7 @@ class Pool {
 
 }  // namespace
 
-struct Node {
+struct Node : GraphSizes {  // the global corpus's graph offsets and run 0
   std::vector<Shard> sh;
   Pool *pool = nullptr;  // one thread per shard (P > 1)
   bool rccl = false;
@@ -127,10 +127,8 @@ struct Node {
   uint32_t n_runs = 0, G = 0, T = 0;
   uint64_t V = 0, E = 0;
   std::vector<uint32_t> iteration;
-  std::vector<uint64_t> node_off, edge_off;
   std::unordered_map<uint32_t, uint32_t> it2run;
   std::vector<uint32_t> run_shard, run_local;  // owner shard / local index of every run
-  int32_t run0 = -1;
   // diff entries of the last diffprov
   uint32_t n_entries = 0;
   std::vector<uint32_t> entry_shard, entry_local;
@@ -305,10 +303,10 @@ static void build_shard_corpus(const nemo_corpus *in, Shard &s, nemo_corpus *out
   for (size_t i = 0; i < R; i++) {
     const uint32_t r = s.runs[i];
     s.it[i] = in->iteration[r];
+    const uint64_t *no = in->node_off + 2 * r, *eo = in->edge_off + 2 * r;  // the run's two graphs
     for (int k = 0; k < 2; k++) {
-      const uint32_t g = 2 * r + k;
-      s.no[2 * i + k + 1] = s.no[2 * i + k] + (in->node_off[g + 1] - in->node_off[g]);
-      s.eo[2 * i + k + 1] = s.eo[2 * i + k] + (in->edge_off[g + 1] - in->edge_off[g]);
+      s.no[2 * i + k + 1] = s.no[2 * i + k] + (no[k + 1] - no[k]);
+      s.eo[2 * i + k + 1] = s.eo[2 * i + k] + (eo[k + 1] - eo[k]);
     }
   }
   const uint64_t V = s.no[2 * R], E = s.eo[2 * R];
@@ -603,7 +601,7 @@ static int node_diff(nemo_ctx *c, const uint32_t *failed, size_t nf, int mode, c
   uint32_t r0f;
   if (int rc = owner_of_iter(c, n, failed[0], &r0f)) return rc;
   const uint32_t root = n->run_shard[r0f];
-  const uint64_t cap = n->node_off[2 * r0f + 2] - n->node_off[2 * r0f + 1] + 1;
+  const uint64_t cap = n->nv(2 * r0f + 1) + 1;
   for (auto &s : n->sh)
     if (s.lab_cap < cap) {
       HCHK(c, hipSetDevice(s.device));
@@ -660,10 +658,6 @@ int node_goal_labels(nemo_ctx *c, uint32_t iteration, int cond, uint32_t *d_out,
   return NEMO_OK;
 }
 
-static uint64_t v0_of(const Node *n) {
-  return n->run0 >= 0 ? n->node_off[2 * n->run0 + 2] - n->node_off[2 * n->run0 + 1] : 0;
-}
-
 int node_fetch_diff_mask(nemo_ctx *c, uint32_t entry, uint8_t *out, uint64_t cap) {
   Node *n = N(c);
   if (entry >= n->n_entries) return fail(c, NEMO_ERR_INVALID, "diff entry %u out of range", entry);
@@ -673,7 +667,7 @@ int node_fetch_diff_mask(nemo_ctx *c, uint32_t entry, uint8_t *out, uint64_t cap
 }
 int node_fetch_diff_masks(nemo_ctx *c, uint8_t *out, uint64_t cap) {
   Node *n = N(c);
-  const uint64_t V0 = v0_of(n);
+  const uint64_t V0 = n->V0();
   if (!out) return fail(c, NEMO_ERR_INVALID, "null output");
   if (cap < n->n_entries * V0) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   return fanout(c, n, [&](Shard &s, size_t) {
@@ -688,7 +682,7 @@ int node_fetch_diff_masks(nemo_ctx *c, uint8_t *out, uint64_t cap) {
 int node_diff_masks_view(nemo_ctx *c, const uint8_t **masks, uint64_t *n_entries, uint64_t *v0) {
   Node *n = N(c);
   if (!masks) return fail(c, NEMO_ERR_INVALID, "null output");
-  const uint64_t V0 = v0_of(n);
+  const uint64_t V0 = n->V0();
   *masks = nullptr;
   if (n_entries) *n_entries = n->n_entries;
   if (v0) *v0 = V0;
@@ -738,7 +732,7 @@ int node_diff_classes(nemo_ctx *c) {
   n->dc_done = false;
   if (int rc = fanout(c, n, [](Shard &s, size_t) { return nemo_diff_classes(s.ctx); })) return rc;
   const size_t P = n->sh.size();
-  const uint64_t V0 = v0_of(n);
+  const uint64_t V0 = n->V0();
   struct Item {
     uint32_t rep, shard, cls, nodes;
     dclass::Hash h;
@@ -838,7 +832,7 @@ int node_fetch_node_flags(nemo_ctx *c, uint32_t g_lo, uint32_t g_hi, uint8_t *ou
     const uint32_t r = g / 2;
     Shard &s = n->sh[n->run_shard[r]];
     const uint32_t lg = 2 * n->run_local[r] + (g & 1);
-    const uint64_t nv = n->node_off[g + 1] - n->node_off[g];
+    const uint64_t nv = n->nv(g);
     SCHK(c, s, nemo_fetch_node_flags(s.ctx, lg, lg + 1, out + (n->node_off[g] - n->node_off[g_lo]), nv));
   }
   return NEMO_OK;
