@@ -648,6 +648,51 @@ func (n *Neo4J) PairDiffProv(pairs [][2]uint) ([]*PairDiff, error) {
 	return res, nil
 }
 
+// NearestRun names, for one query run, the candidate run whose derived post
+// goals are nearest to its own.
+type NearestRun struct {
+	Query       uint // iteration
+	Nearest     uint // iteration of the nearest candidate (valid only if Found)
+	Found       bool // false: no candidate but the query itself
+	Dist        uint // labels of post goals only one of the two runs derived
+	OnlyQuery   uint // ... that only the query derived
+	OnlyNearest uint // ... that only the candidate derived
+}
+
+// NearestRuns picks the partner of every query run for PairDiffProv
+// (nemo_nearest_runs): the candidate whose set of post-goal labels differs
+// least from the query's, ties to the earlier candidate, the query itself
+// skipped.  The reference has no counterpart, it compares with run 0 only.
+func (n *Neo4J) NearestRuns(queries, candidates []uint) ([]*NearestRun, error) {
+	qs, cs := make([]C.uint32_t, len(queries)+1), make([]C.uint32_t, len(candidates)+1)
+	for i, it := range queries {
+		qs[i] = C.uint32_t(it)
+	}
+	for j, it := range candidates {
+		cs[j] = C.uint32_t(it)
+	}
+	if err := n.err(C.nemo_nearest_runs(n.ctx, &qs[0], C.size_t(len(queries)), &cs[0], C.size_t(len(candidates)))); err != nil {
+		return nil, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_nearest(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	near := make([]C.nemo_nearest, cnt+1)
+	if err := n.err(C.nemo_fetch_nearest(n.ctx, &near[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	res := make([]*NearestRun, len(queries))
+	for i, it := range queries {
+		res[i] = &NearestRun{Query: it}
+		if j := uint32(near[i].cand); j != ^uint32(0) {
+			res[i].Nearest, res[i].Found = candidates[j], true
+			res[i].Dist, res[i].OnlyQuery, res[i].OnlyNearest = uint(near[i].dist), uint(near[i].only_query), uint(near[i].only_cand)
+		}
+	}
+	return res, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

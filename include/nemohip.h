@@ -213,7 +213,15 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       (test knob, as "class_hash_bits")
  *   "pair_hash_lds_max" largest label table (slots) nemo_diffprov_pairs builds in
  *                       LDS; larger ones are built in place with global atomics
- *                       (default and upper bound 16384; 0 = every table in place) */
+ *                       (default and upper bound 16384; 0 = every table in place)
+ *   "near_bits_lds_max" largest bit row (bytes) nemo_nearest_runs builds in LDS;
+ *                       longer rows are zeroed in place and filled with global
+ *                       atomics (default and upper bound 65536; 0 = every row in place)
+ *   "near_ksplit"       ranges the row words (K) of nemo_nearest_runs' intersection
+ *                       counts are split into, each range a workgroup per tile, summed
+ *                       with integer atomics (0, default: one range unless the tiles
+ *                       alone leave the device under two workgroups per CU; at most
+ *                       1024 and the K-slabs of a row)                                */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -404,6 +412,48 @@ int nemo_fetch_surplus(nemo_ctx *ctx, nemo_missing *out, uint64_t cap, uint64_t 
  * ahead of the walk (an entry against iteration 0 uses the table of the load).
  * Single-device contexts only (a node context returns NEMO_ERR_STATE).       */
 int nemo_diffprov_pairs(nemo_ctx *ctx, const uint32_t *base_iters, const uint32_t *other_iters, size_t n);
+
+/* ---- nearest runs by post-goal label sets -------------------------------------
+ * Which run to give nemo_diffprov_pairs as `other`: for every query run, the
+ * candidate run whose derived post goals are closest to its own.  The reference
+ * has no counterpart (it compares with run 0 only); the call steers the pair
+ * diff as nemo_diff_classes summarises the diff.
+ * L(r) = the distinct labels of the goal nodes of run r's raw post graph (the
+ * key set of the pair diff's label table of r).  For a query q and a candidate c
+ *   only_query = |L(q) \ L(c)|,  only_cand = |L(c) \ L(q)|,
+ *   dist = only_query + only_cand = |L(q)| + |L(c)| - 2 |L(q) & L(c)|.
+ * The row of query position i names the candidate position j of least dist;
+ * ties go to the smallest j; candidates whose iteration equals the query's
+ * iteration are skipped (a run is not its own neighbour).  If no candidate is
+ * left (n_c == 0, or every candidate is the query itself), cand and the three
+ * counts are UINT32_MAX.  only_query == 0 exactly when the S mask of the pair
+ * (q, c) of nemo_diffprov_pairs is all zero: Bad(q, c) is the goals of q whose
+ * label is missing from c.
+ * Needs nemo_load_corpus only.  Both lists may name any loaded run, duplicates
+ * included; run 0 need not be loaded; an iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; n_q == 0 gives zero rows and NEMO_OK.  n_q * n_c > 2^30, or
+ * a bit matrix (distinct runs of the call x ceil((largest goal label + 1) / 64)
+ * words, rows rounded up to 16 bytes) past 2^36 bytes, is NEMO_ERR_LIMIT: tile
+ * the queries (labels are interned ids; the second limit is what sparse ids
+ * meet).  Single-device contexts only (a node context returns NEMO_ERR_STATE).
+ * Everything runs on the device on the context's stream; the call blocks until
+ * the rows are on the host, as nemo_diff_classes does.  The state is the call's
+ * own: valid until the next nemo_nearest_runs or nemo_load_corpus (the fetches
+ * return NEMO_ERR_STATE otherwise), independent of every diff state in both
+ * directions.                                                                 */
+typedef struct nemo_nearest {
+  uint32_t cand;       /* position in cand_iters (UINT32_MAX: no candidate left)     */
+  uint32_t dist;       /* only_query + only_cand                                     */
+  uint32_t only_query; /* labels of the query's post goals the candidate lacks       */
+  uint32_t only_cand;  /* labels of the candidate's post goals the query lacks       */
+} nemo_nearest;
+int nemo_nearest_runs(nemo_ctx *ctx, const uint32_t *query_iters, size_t n_q, const uint32_t *cand_iters, size_t n_c);
+/* out[i] for every query position i; out == NULL queries *n_out (= n_q).       */
+int nemo_fetch_nearest(nemo_ctx *ctx, nemo_nearest *out, uint64_t cap, uint64_t *n_out);
+/* Rows [q_lo, q_hi) of the n_q x n_c distance matrix (dist of every pair of list
+ * positions, self-pairs with their true distance 0), copied from the device:
+ * for callers that want the k nearest; cap >= (q_hi - q_lo) * n_c.             */
+int nemo_fetch_label_distances(nemo_ctx *ctx, uint32_t q_lo, uint32_t q_hi, uint32_t *out, uint64_t cap);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

@@ -295,6 +295,14 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.pair_hash_lds_max = value < 0 ? LAB_HASH_LDS_SLOTS : (uint32_t)std::min<int64_t>(value, LAB_HASH_LDS_SLOTS);
     return NEMO_OK;
   }
+  if (!strcmp(name, "near_bits_lds_max")) {  // largest bit row (bytes) k_near_bits builds in LDS; 0: every row in place
+    c->opt.near_bits_lds_max = value < 0 ? NEAR_LDS_MAX : (uint32_t)std::min<int64_t>(value, NEAR_LDS_MAX);
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "near_ksplit")) {  // K ranges of k_near_isect; 0 / -1: by the tile count and the device
+    c->opt.near_ksplit = value < 0 ? 0u : (uint32_t)std::min<int64_t>(value, NEAR_MAX_KSPLIT);
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;

@@ -19,6 +19,7 @@
 #include "device.h"
 #include "gdedup_host.h"
 #include "internal.h"
+#include "nearest_host.h"
 #include "node.h"
 #include "pairs_host.h"
 
@@ -145,6 +146,8 @@ struct Options {
   bool graph_dedup = true;    // option graph_dedup: the per-graph kernels run on one graph per distinct content
   int dedup_hash_bits = 128;  // the load's duplicate classes bucket by the low k bits of the hash (test knob)
   uint32_t pair_hash_lds_max = LAB_HASH_LDS_SLOTS;  // largest label table (slots) k_lab_hash builds in LDS (0: none)
+  uint32_t near_bits_lds_max = NEAR_LDS_MAX;  // largest bit row (bytes) k_near_bits builds in LDS (0: none)
+  uint32_t near_ksplit = 0;                   // k_near_isect's K ranges (0: by the tile count and the device)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -259,6 +262,19 @@ struct CorpusState : GraphSizes {
   std::vector<nemo::LabTab> sd_tabs;  // the last call's upload
   DevBuf<uint32_t> d_phreg;          // u32 slots, exactly the largest request so far
 
+  // nearest runs (k_near.hip): the call's own state, void after the next call or load; independent of every
+  // diff state.  near_lmax is the load's (found at the first call); the five buffers grow together, only inside
+  // nemo_nearest_runs, in this order
+  bool near_lmax_done = false, near_done = false;
+  uint32_t near_lmax = 0, near_nq = 0, near_nc = 0;
+  DevBuf<uint32_t> d_nrlmax;         // [1]
+  DevBuf<uint64_t> d_nrbits;         // [rows][W]
+  DevBuf<uint32_t> d_nrsize;         // [rows]
+  DevBuf<uint32_t> d_nrmat;          // [n_q][n_c] intersections, then distances
+  DevBuf<uint32_t> d_nrout;          // [n_q][4] nemo_nearest rows
+  DevBuf<uint32_t> d_nrdesc;         // [rows] post graphs | [n_q] query rows | [n_c] candidate rows
+  std::vector<uint32_t> nr_desc;     // the last call's upload
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -336,10 +352,11 @@ struct nemo_ctx {
   // queued so far, beside the triggers and pulls queued after
   hipEvent_t ev_stage = nullptr;
   hipEvent_t ev_dclass = nullptr;  // nemo_diff_classes' hashes / verdicts have reached pinned memory
-  hipEvent_t *const events[19] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_near = nullptr;    // nemo_nearest_runs' label maximum / rows have reached pinned memory
+  hipEvent_t *const events[20] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
-                                  &ev_dclass};
+                                  &ev_dclass,  &ev_near};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -350,11 +367,12 @@ struct nemo_ctx {
   PullHost h_pull;
   // nemo_diff_classes: h_dcin uploads (entry counts, pairs), h_dcout receives (hashes, |D|, support, verdicts)
   Pinned<uint32_t> h_dcin, h_dcout;
-  void **const pinned[21] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint32_t> h_near;  // nemo_nearest_runs: [n_q][4] rows, then the label maximum
+  void **const pinned[22] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
-                             h_dcin.slot(),  h_dcout.slot()};
+                             h_dcin.slot(),  h_dcout.slot(),   h_near.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

@@ -148,6 +148,20 @@ struct SdiffArgs {
   uint32_t *n_rows;         // counter
 };
 
+// One nemo_nearest_runs call (k_near.hip): a bit row of W u64 words per distinct run of the call (bit
+// `label` set for every goal label of its post graph), and the n_q x n_c matrix over list positions.
+struct NearArgs {
+  const uint32_t *row_graph;  // [rows] the post graph of each bit row
+  uint64_t *bits;             // [rows][W], 16-byte aligned rows (W is even)
+  uint32_t *size;             // [rows] |L(r)|: the distinct goal labels
+  uint32_t rows;
+  uint64_t W;
+  const uint32_t *qrow, *crow;  // [n_q], [n_c] the bit row of every query / candidate position
+  uint32_t n_q, n_c;
+  uint32_t *mat;              // [n_q][n_c] intersection counts (zeroed per call under split-K), then distances
+  uint32_t *out;              // [n_q][4] nemo_nearest rows: cand, dist, only_query, only_cand
+};
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)
@@ -228,6 +242,14 @@ void launch_sdiff(const DevCorpus &c, const SdiffArgs &a, uint32_t n_entries, ui
 #define LAB_HASH_LDS_SLOTS 16384u  // the LDS path's budget: 64 KB, two workgroups per CU
 void launch_lab_hash(const DevCorpus &c, const LabTab *tabs, uint32_t n_tabs, uint32_t lds_max, uint32_t lds_slots,
                      hipStream_t s);
+// nemo_nearest_runs (k_near.hip).  lmax: the largest goal label of the post graphs, atomicMax'ed into a
+// zeroed word by `parts` workgroups per run; bit rows of at most lds_max bytes are built in LDS, larger
+// ones in place; the tile / split-K grid is nearest_host.h's
+void launch_near_lmax(const DevCorpus &c, uint32_t parts, uint32_t *lmax, hipStream_t s);
+void launch_near_bits(const DevCorpus &c, const NearArgs &a, uint32_t lds_max, hipStream_t s);
+void launch_near_isect(const NearArgs &a, uint64_t tq, uint64_t tc, uint32_t slabs, uint32_t slabs_per_split,
+                       uint32_t ksplit, hipStream_t s);
+void launch_near_pick(const NearArgs &a, hipStream_t s);
 uint32_t dclass_rows_per_block(uint64_t V0, uint32_t nu);
 void launch_dclass_hash(const DclassArgs &a, hipStream_t s);
 // verdict[k] = 1 iff rows pairs[2k] and pairs[2k + 1] (sources) have the same membership at every node

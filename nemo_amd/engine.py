@@ -36,6 +36,10 @@ class CTiming(ctypes.Structure):
                 ("bytes", ctypes.c_double), ("edges", ctypes.c_double)]
 
 
+# struct nemo_nearest (nemo_fetch_nearest)
+NEAREST_DTYPE = np.dtype([("cand", np.uint32), ("dist", np.uint32), ("only_query", np.uint32), ("only_cand", np.uint32)])
+
+
 def header_symbols() -> List[str]:
     """Every function the C ABI header declares."""
     txt = open(HEADER).read()
@@ -101,6 +105,9 @@ def lib():
             "nemo_diffprov_pairs": ([vp, vp, vp, sz], i32),
             "nemo_fetch_sdiff_masks": ([vp, vp, vp, u64, P(u64)], i32),
             "nemo_fetch_surplus": ([vp, vp, u64, P(u64)], i32),
+            "nemo_nearest_runs": ([vp, vp, sz, vp, sz], i32),
+            "nemo_fetch_nearest": ([vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_label_distances": ([vp, u32, u32, vp, u64], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -288,6 +295,31 @@ class Engine:
         self._n_sym = 0
         self._chk(self.L.nemo_diffprov_pairs(self.h, _p(b), _p(o), len(b)))
         self._n_sym = len(b)
+
+    def nearest_runs(self, queries: Sequence[int], candidates: Sequence[int]) -> np.ndarray:
+        """nemo_nearest_runs: for every query iteration, the position in `candidates` of the run whose
+        post-goal label set is nearest to its own (ties to the smallest position, the query's own run
+        skipped).  Returns the rows as a structured array (NEAREST_DTYPE: cand, dist, only_query,
+        only_cand; all UINT32_MAX where no candidate is left)."""
+        q = np.ascontiguousarray(queries, dtype=np.uint32)
+        c = np.ascontiguousarray(candidates, dtype=np.uint32)
+        self._near = (0, 0)
+        self._chk(self.L.nemo_nearest_runs(self.h, _p(q), len(q), _p(c), len(c)))
+        self._near = (len(q), len(c))
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_nearest(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, NEAREST_DTYPE)
+        self._chk(self.L.nemo_fetch_nearest(self.h, _p(out), len(out), ctypes.byref(n)))
+        return out
+
+    def label_distances(self, q_lo: int = 0, q_hi: Optional[int] = None) -> np.ndarray:
+        """nemo_fetch_label_distances: rows [q_lo, q_hi) of the last nearest_runs call's distance matrix,
+        [q_hi - q_lo, n_candidates] u32 (self-pairs carry their true distance 0)."""
+        n_q, n_c = getattr(self, "_near", (0, 0))
+        q_hi = n_q if q_hi is None else q_hi
+        out = np.zeros((max(q_hi - q_lo, 0), n_c), np.uint32)
+        self._chk(self.L.nemo_fetch_label_distances(self.h, q_lo, q_hi, _p(out), out.size))
+        return out
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
         """nemo_goal_labels: [n, label...] of a run's goal labels into device memory."""

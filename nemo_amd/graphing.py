@@ -410,6 +410,25 @@ class Neo4J:
         dots, events = self._surplus_dots(base)
         return [{"Base": b, "Other": o, "Dot": dots[e], "Surplus": events[e]} for e, (b, o) in enumerate(pairs)]
 
+    def NearestRuns(self, queries: Sequence[int], candidates: Sequence[int]) -> List[dict]:
+        """For every query run, the candidate run whose derived post goals are nearest to its own
+        (nemo_nearest_runs: the distance is the size of the symmetric difference of the two runs'
+        post-goal label sets; ties go to the earlier candidate, the query itself is skipped).  It has
+        no reference counterpart: differential-provenance.go compares every failed run with run 0.
+        One record per query, in order: {"Query", "Nearest": the candidate's iteration (None when no
+        candidate is left), "Dist", "OnlyQuery", "OnlyNearest"}.  The output is meant as the `pairs`
+        argument of PairDiffProv: [(r["Query"], r["Nearest"]) for r in records if r["Nearest"] is not
+        None] compares every failed run with the good run that derived almost the same goals."""
+        queries = [int(q) for q in queries]
+        candidates = [int(c) for c in candidates]
+        rows = self.eng.nearest_runs(queries, candidates)
+        none = 0xFFFFFFFF
+        return [{"Query": q, "Nearest": None if int(r["cand"]) == none else candidates[int(r["cand"])],
+                 "Dist": None if int(r["cand"]) == none else int(r["dist"]),
+                 "OnlyQuery": None if int(r["cand"]) == none else int(r["only_query"]),
+                 "OnlyNearest": None if int(r["cand"]) == none else int(r["only_cand"])}
+                for q, r in zip(queries, rows)]
+
     def _surplus_dots(self, failedRuns: Sequence[int]):
         """(marked DOTs, surplus events) of the last symmetric / pairs call, whose entries walked the
         post graphs of failedRuns."""
