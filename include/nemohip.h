@@ -211,6 +211,25 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       content hash, k in 0..128 (default 128; takes effect at the
  *                       next load); every bucket is confirmed by exact comparisons
  *                       (test knob, as "class_hash_bits")
+ *   "proto_dedup"       1 (default, also -1): while "graph_dedup" has duplicates, the
+ *                       runs whose pre graphs are of one class and whose post graphs
+ *                       are form a run class; the prototype kernel of the LDS tier
+ *                       runs on the lowest run of each class and its rows (prototype
+ *                       bits, graph tables, gate) are copied to the others.  0: it
+ *                       runs every run
+ *   "pull_dedup"        1 (default, also -1): while "graph_dedup" has duplicates,
+ *                       nemo_pull_edges 0 / 1 compacts one graph per class and the
+ *                       other graphs' slots share its region (same edges in the
+ *                       same order; see nemo_fetch_pulled_all).  0: every graph is
+ *                       compacted into a region of its own
+ *   "replicate_lazy"    1 (default, also -1): under "graph_dedup", "proto_dedup" and
+ *                       "pull_dedup", once a pass has shown every global tier
+ *                       empty, a load / rebuild copies only the per-graph scalars
+ *                       to the duplicates; their CSR, Kahn and e2 slices follow
+ *                       before the first call that may read them (any fetch of
+ *                       graph data, the symmetric / pair diff, nearest runs,
+ *                       failure classes, an option change).  0: right behind the
+ *                       build, every time
  *   "pair_hash_lds_max" largest label table (slots) nemo_diffprov_pairs builds in
  *                       LDS; larger ones are built in place with global atomics
  *                       (default and upper bound 16384; 0 = every table in place)
@@ -510,7 +529,10 @@ int nemo_fetch_pulled(nemo_ctx *ctx, uint32_t slot, uint32_t *src, uint32_t *dst
  * in src/dst, whose used extent is *n_used (regions are claimed in device
  * order, so they are not sorted by slot; they are disjoint, except that diff
  * entries sharing a label source -- one D mask, one graph -- share one
- * region).  src/dst may be NULL to query *n_used; then cap >= *n_used.     */
+ * region, and so do, under "graph_dedup" with "pull_dedup", the graphs of
+ * identical content of a which 0/1 pull: node indices are graph-local, so
+ * their edge lists are one list, and the sum of cnt[] then exceeds *n_used).
+ * src/dst may be NULL to query *n_used; then cap >= *n_used.               */
 int nemo_fetch_pulled_all(nemo_ctx *ctx, uint64_t *off, uint32_t *cnt, uint32_t *src, uint32_t *dst, uint64_t cap,
                           uint64_t *n_used);
 

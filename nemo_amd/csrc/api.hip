@@ -14,6 +14,13 @@ static void set_graph_dedup(nemo_ctx *c) {
   const bool on = c->opt.graph_dedup && c->cs.gd_npairs != 0;
   c->cs.dc.dd_list = on ? c->cs.d_gd_list : nullptr;
   c->cs.dc.dd_n = on ? c->cs.gd_nlist : 0;
+  c->cs.dc.dd_rep = on ? c->cs.d_gd_rep : nullptr;
+  // ... and the runs' list: the representative runs, under the same conditions and option proto_dedup
+  const bool runs = on && c->opt.proto_dedup && c->cs.gd_nrpairs != 0;
+  c->cs.dc.run_list = runs ? c->cs.d_gd_rlist : nullptr;
+  c->cs.dc.run_pairs = runs ? c->cs.d_gd_rpairs : nullptr;
+  c->cs.dc.run_n = runs ? c->cs.gd_nrlist : 0;
+  c->cs.dc.run_npairs = runs ? c->cs.gd_nrpairs : 0;
 }
 // a replicate pass behind `phase`'s kernel (k_gdedup.hip); nothing without duplicates
 static int replicate(nemo_ctx *c, int phase) {
@@ -173,6 +180,10 @@ int nemo_set_stream(nemo_ctx *c, void *stream) {
 int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
   DISPATCH(node_set_option(c, name, value));
   if (!c || !name) return NEMO_ERR_INVALID;
+  if (c->cs.gd_stale) {  // the kernels after an option change may read any graph's slices
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rw = ensure_whole(c)) return rw;
+  }
   tiers_reset(c);  // any option may move graphs between tiers
   c->cs.ms_fused = false;  // ... and the fused tail's graphs were chosen under the old caps
   if (!strcmp(name, "chains_lds_max")) {
@@ -284,6 +295,19 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
   if (!strcmp(name, "graph_dedup")) {  // 0: every graph runs its own workgroup, nothing is replicated
     c->opt.graph_dedup = value != 0;
     set_graph_dedup(c);
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "proto_dedup")) {  // 0: k_proto_lds runs every run; 1 / -1: one run per run class
+    c->opt.proto_dedup = value != 0;
+    set_graph_dedup(c);
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "replicate_lazy")) {  // 0: k_build's slices reach the duplicates right behind k_build; 1 / -1: on demand
+    c->opt.replicate_lazy = value != 0;
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "pull_dedup")) {  // 0: raw / simplified pulls compact every graph; 1 / -1: one graph per class
+    c->opt.pull_dedup = value != 0;  // (read by the next nemo_pull_edges; a pull already queued keeps its slots)
     return NEMO_OK;
   }
   if (!strcmp(name, "dedup_hash_bits")) {  // test knob: 0..128 low hash bits bucket the graphs; takes effect at the next load
@@ -500,7 +524,25 @@ static int device_load(nemo_ctx *c, const LoadParts *lp = nullptr) {
   if ((rc = timed(c, "k_build", 16 * Eb + (c->cs.dc.ms_fuse ? 21 : 20) * Vb + 4 * Ep + 4 * Vp, 2 * Eb,
                   [&] { nemo::launch_build(c->cs.dc, c->stream); })))
     return rc;
-  if ((rc = replicate(c, GD_BUILD))) return rc;  // before k_load_sel reads the duplicates' redo flags
+  // The duplicates' scalars (redo, err, created, nlev) at once: k_load_sel reads redo and many kernels err of
+  // every graph.  Their slices wait for ensure_whole when the host knows that the pass reads the slices of
+  // representatives only: every graph inside k_marksimp's and the pull's LDS tiers, the three global tiers
+  // known to be empty (so this is never the first pass after a load or an option), and k_proto_lds and the
+  // pulls over the classes.  In any other case both go out in one launch, as before.
+  c->cs.gd_stale = false;
+  if (c->cs.dc.dd_list) {
+    const bool lazy = c->opt.replicate_lazy && c->cs.dc.run_list && c->opt.pull_dedup && c->cs.dc.t_ms.bytes &&
+                      c->cs.ms_rest == 0 && c->cs.pull_rest == 0 && tier_empty(c, 0) && tier_empty(c, 1) && tier_empty(c, 2);
+    if (lazy) {
+      if ((rc = timed(c, "k_build", 0, 0, [&] {
+            nemo::launch_replicate(c->cs.dc, c->cs.d_gd_pairs, c->cs.gd_npairs, GD_BUILD_SCALARS, c->stream);
+          })))
+        return rc;
+      c->cs.gd_stale = true;
+    } else if ((rc = replicate(c, GD_BUILD))) {
+      return rc;
+    }
+  }
   c->cs.ms_fused = c->cs.dc.ms_fuse != 0;
   // graphs past k_build: k_csr (one workgroup per graph) below NEMO_CSR_BIG nodes, k_csrb_* above
   const double Eg = std::max(0.0, E - c->cs.bigE), Vg = std::max(0.0, V - c->cs.bigV);
@@ -860,7 +902,8 @@ static int load_graph_classes(nemo_ctx *c, bool dbg) {
   uint8_t *d_verdict = nullptr;
   int rc;
   if ((rc = dalloc(c, &d_hash, 2 * (size_t)G)) || (rc = dalloc(c, &s.d_gd_list, G)) ||
-      (rc = dalloc(c, &s.d_gd_pairs, 2 * (size_t)G)) || (rc = dalloc(c, &d_verdict, G)))
+      (rc = dalloc(c, &s.d_gd_pairs, 2 * (size_t)G)) || (rc = dalloc(c, &d_verdict, G)) ||
+      (rc = dalloc(c, &s.d_gd_rlist, G / 2)) || (rc = dalloc(c, &s.d_gd_rpairs, G)) || (rc = dalloc(c, &s.d_gd_rep, G)))
     return rc;
   hipStream_t st = c->stream;
   nemo::launch_gd_hash(s.dc, d_hash, st);
@@ -894,7 +937,16 @@ static int load_graph_classes(nemo_ctx *c, bool dbg) {
   if (s.gd_npairs) {
     HIPCHK(c, hipMemcpyAsync(s.d_gd_list, p.list.data(), 4 * p.list.size(), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(s.d_gd_pairs, p.pairs.data(), 4 * p.pairs.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st));  // the plan goes out of scope
+    HIPCHK(c, hipMemcpyAsync(s.d_gd_rep, p.rep.data(), 4 * p.rep.size(), hipMemcpyHostToDevice, st));
+    // the run classes: without a duplicate graph no run is a duplicate
+    gdedup::RunPlan rp = gdedup::run_plan(p.rep);
+    s.gd_nrlist = (uint32_t)rp.list.size();
+    s.gd_nrpairs = (uint32_t)(rp.pairs.size() / 2);
+    if (s.gd_nrpairs) {
+      HIPCHK(c, hipMemcpyAsync(s.d_gd_rlist, rp.list.data(), 4 * rp.list.size(), hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(s.d_gd_rpairs, rp.pairs.data(), 4 * rp.pairs.size(), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));  // the plans go out of scope
     double dv = 0, de = 0, dvp = 0, dep = 0;
     for (uint32_t k = 0; k < s.gd_npairs; k++) {
       const uint32_t g = p.pairs[2 * k];
@@ -984,6 +1036,7 @@ int nemo_mark_holds(nemo_ctx *c) {
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "nemo_mark_holds before nemo_load_corpus");
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: k_mark / k_mw_mark_* read the build outputs of no duplicate while the slices are stale (device_load)
   if (int rl = ensure_load_checked(c)) return rl;
   const double V = (double)c->cs.V - c->cs.tierV, E = (double)c->cs.E - c->cs.tierE;
   int rc = guard_staged(c);
@@ -1003,6 +1056,7 @@ int nemo_simplify(nemo_ctx *c) {
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "nemo_simplify before nemo_mark_holds");
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: k_marksimp, k_chains and the replicates read the build outputs of representatives only (device_load)
   int rc = guard_staged(c);
   if (rc) return rc;
   if (c->cs.mark_pending) {
@@ -1050,6 +1104,7 @@ int nemo_protos_partial(nemo_ctx *c, const uint32_t *success_iters, size_t n_suc
   if (!c->cs.simplified) return fail(c, NEMO_ERR_STATE, "nemo_protos_partial before nemo_simplify");
   if (!d_red) d_red = c->cs.d_red;  // single-process callers use the context's own vector
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: k_proto_lds reads a post graph's build outputs through its representative; k_reduce reads none
   if (c->cs.red_staged) {  // a staged copy of an older vector: wait for it, then forget it
     HIPCHK(c, hipEventSynchronize(c->ev_red));
     c->cs.red_staged = nullptr;
@@ -1138,6 +1193,7 @@ int nemo_protos_stage(nemo_ctx *c, const uint32_t *d_red) {
   if (!d_red) return fail(c, NEMO_ERR_STATE, "nemo_protos_stage before nemo_load_corpus");
   if (!c->cs.protos_done) return fail(c, NEMO_ERR_STATE, "nemo_protos_stage before nemo_protos_partial");
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: reads no graph
   return protos_stage(c, d_red);
 }
 
@@ -1149,6 +1205,7 @@ int nemo_protos_finalize(nemo_ctx *c, const uint32_t *d_red, uint32_t *achieved,
   if (!d_red) d_red = c->cs.d_red;
   if (!d_red) return fail(c, NEMO_ERR_STATE, "nemo_protos_finalize before nemo_load_corpus");
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: reads no graph
   const uint32_t T = c->cs.T;
   int rc;
   if (c->cs.red_staged != d_red && (rc = protos_stage(c, d_red))) return rc;
@@ -1167,6 +1224,7 @@ int nemo_fetch_reduce(nemo_ctx *c, uint32_t *out, uint64_t cap) {
   const uint64_t n = 2 * (uint64_t)c->cs.T + 4;
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)n);
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   HIPCHK(c, hipMemcpyAsync(out, c->cs.d_red, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NEMO_OK;
@@ -1189,6 +1247,7 @@ int nemo_fetch_run_tables(nemo_ctx *c, int which, uint32_t *out, uint64_t cap) {
   const uint64_t n = (uint64_t)c->cs.n_runs * c->cs.W;
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)n);
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: reads the per-run table sets, no graph
   HIPCHK(c, hipEventSynchronize(c->ev_protos));
   memcpy(out, c->h_tab.p + (which == 0 ? 0 : n), n * 4);
   return NEMO_OK;
@@ -1203,6 +1262,7 @@ int nemo_missing_from(nemo_ctx *c, uint32_t failed_iter, const uint32_t *proto, 
   int rc = run_index(c, failed_iter, &r);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   std::vector<uint32_t> bits(c->cs.W);
   HIPCHK(c, hipMemcpyAsync(bits.data(), c->cs.dc.graph_tables + (size_t)r * c->cs.W, c->cs.W * 4, hipMemcpyDeviceToHost,
                            c->stream));
@@ -1246,9 +1306,13 @@ int nemo_debug_copy(nemo_ctx *c, const char *name, void *out, uint64_t offset, u
   else if (n == "s_a") base = c->cs.dc.s_a;
   else if (n == "gscratch") base = c->cs.dc.gscratch;
   else if (n == "gs_off") base = c->cs.dc.gs_off;
+  else if (n == "run_list") base = c->cs.dc.run_list;  // the representative runs / (dup, rep) run pairs while in use
+  else if (n == "run_pairs") base = c->cs.dc.run_pairs;
+  else if (n == "gate") base = c->cs.dc.gate;
   else if (n == "err") base = c->cs.dc.err;  // worklists: [4][G+1] u32, count first (pulls, chains, load, protos)
   if (!base) return fail(c, NEMO_ERR_INVALID, "unknown array %s", name);
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   int rc = join_aux(c);  // the diff kernels on `aux` write dbits, dmask and the Kahn relayout
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(out, (const char *)base + offset, bytes, hipMemcpyDeviceToHost, c->stream));

@@ -14,6 +14,7 @@ static int diffprov_impl(nemo_ctx *c, const uint32_t *failed_iters, size_t n_fai
   if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "nemo_diffprov before nemo_mark_holds");
   // (the diff kernels read no holds flags: a deferred mark stays fused with the simplification)
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   c->cs.n_entries = 0;
   c->cs.dc_done = false;  // the classes were those of the previous call's masks
   c->cs.diff_done = n_failed == 0 || c->cs.run0 < 0;
@@ -249,6 +250,7 @@ int nemo_goal_labels(nemo_ctx *c, uint32_t iteration, int cond, uint32_t *d_out,
   if (!c || !d_out || (cond != 0 && cond != 1)) return NEMO_ERR_INVALID;
   if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "no corpus loaded");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   if (int rl = ensure_load_checked(c)) return rl;
   uint32_t r;
   int rc = run_index(c, iteration, &r);
@@ -269,6 +271,7 @@ int nemo_fetch_diff_mask(nemo_ctx *c, uint32_t entry, uint8_t *out, uint64_t cap
   const uint64_t V0 = c->cs.V0();
   if (cap < V0) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   HIPCHK(c, hipEventSynchronize(c->ev_diff));
   memcpy(out, c->h_mask.p + (size_t)entry * V0, V0);
   return NEMO_OK;
@@ -281,6 +284,7 @@ int nemo_fetch_diff_masks(nemo_ctx *c, uint8_t *out, uint64_t cap) {
   const uint64_t n = (uint64_t)c->cs.n_entries * c->cs.V0();
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   HIPCHK(c, hipEventSynchronize(c->ev_diff));
   memcpy(out, c->h_mask.p, n);
   return NEMO_OK;
@@ -294,6 +298,7 @@ int nemo_diff_masks_view(nemo_ctx *c, const uint8_t **masks, uint64_t *n_entries
   if (v0) *v0 = c->cs.V0();
   if (!c->cs.n_entries) return NEMO_OK;
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   HIPCHK(c, hipEventSynchronize(c->ev_diff));
   *masks = c->h_mask.p;
   return NEMO_OK;
@@ -303,6 +308,7 @@ int nemo_fetch_missing(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
   DISPATCH(node_fetch_missing(c, out, cap, n_out));
   if (!c) return NEMO_ERR_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   uint32_t nu_rows = 0;
   if (c->cs.n_entries) {
     HIPCHK(c, hipEventSynchronize(c->ev_diff));
@@ -368,6 +374,7 @@ int nemo_diff_classes(nemo_ctx *c) {
     return NEMO_OK;
   }
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   int rc;
   if ((rc = ensure_event(c, &c->ev_dclass))) return rc;
   hipStream_t s = cs.diff_stream;  // behind the diff kernels, on whichever stream they ran
@@ -445,6 +452,7 @@ int nemo_diff_classes(nemo_ctx *c) {
 
 int nemo_fetch_diff_classes(nemo_ctx *c, uint32_t *class_of, nemo_diff_class *classes, uint64_t cap, uint64_t *n_classes) {
   DISPATCH(node_fetch_diff_classes(c, class_of, classes, cap, n_classes));
+  // no ensure_whole: reads the host results of nemo_diff_classes, no graph
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.dc_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_diff_classes before nemo_diff_classes (or after a later nemo_diffprov)");
   const uint64_t k = c->cs.dc_classes.size();
@@ -458,6 +466,7 @@ int nemo_fetch_diff_classes(nemo_ctx *c, uint32_t *class_of, nemo_diff_class *cl
 
 int nemo_fetch_diff_support(nemo_ctx *c, uint32_t *out, uint64_t cap) {
   DISPATCH(node_fetch_diff_support(c, out, cap));
+  // no ensure_whole: reads the host results of nemo_diff_classes, no graph
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.dc_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_diff_support before nemo_diff_classes (or after a later nemo_diffprov)");
   const uint64_t V0 = c->cs.dc_support.size();
@@ -487,6 +496,7 @@ static int sdiff_impl(nemo_ctx *c, bool per_pair, const uint32_t *failed_iters, 
   if (!c->cs.loaded) return fail(c, NEMO_ERR_STATE, "%s without a loaded corpus (the last load failed?)", who);
   if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "%s before nemo_mark_holds", who);
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   c->cs.n_sentries = 0;
   c->cs.sd_done = false;
   c->cs.sd_graph.clear();
@@ -618,6 +628,7 @@ int nemo_fetch_sdiff_masks(nemo_ctx *c, uint64_t *off, uint8_t *out, uint64_t ca
   if (cap < total) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   if (total) {
     HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
     HIPCHK(c, hipMemcpyAsync(out, c->cs.d_sdmask.p, total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -630,6 +641,7 @@ int nemo_fetch_surplus(nemo_ctx *c, nemo_missing *out, uint64_t cap, uint64_t *n
   uint32_t n = 0;
   if (c->cs.n_sentries) {
     HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
     HIPCHK(c, hipMemcpyAsync(&n, c->cs.d_sdn.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }

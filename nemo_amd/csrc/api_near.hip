@@ -17,6 +17,7 @@ int nemo_nearest_runs(nemo_ctx *c, const uint32_t *query_iters, size_t n_q, cons
   cs.near_done = false;
   cs.near_nq = cs.near_nc = 0;
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   int rc;
   if ((rc = ensure_load_checked(c))) return rc;
   std::vector<uint32_t> q_run(n_q), c_run(n_c);
@@ -136,7 +137,7 @@ int nemo_fetch_nearest(nemo_ctx *c, nemo_nearest *out, uint64_t cap, uint64_t *n
   if (!c) return NEMO_ERR_INVALID;
   if (c->node || !c->cs.near_done)
     return fail(c, NEMO_ERR_STATE, "nemo_fetch_nearest before nemo_nearest_runs (or after a later nemo_load_corpus)");
-  const uint64_t n = c->cs.near_nq;
+  const uint64_t n = c->cs.near_nq;  // no ensure_whole: reads the last call's host rows, no graph
   if (n_out) *n_out = n;
   if (!out) return NEMO_OK;
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
@@ -155,6 +156,7 @@ int nemo_fetch_label_distances(nemo_ctx *c, uint32_t q_lo, uint32_t q_hi, uint32
   if (!out) return NEMO_ERR_INVALID;
   if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   HIPCHK(c, hipMemcpyAsync(out, c->cs.d_nrmat.p + (size_t)q_lo * c->cs.near_nc, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NEMO_OK;

@@ -19,6 +19,7 @@ static int pull_launch(nemo_ctx *c) {
     s = c->aux;
   }
   double V = (double)c->cs.V, E = (double)c->cs.E;
+  if (a.which < 2 && a.slot_g) V = c->cs.pl_V, E = c->cs.pl_E;  // the graphs compacted: one per class
   if (a.which == 2) {
     V = (double)slots * (double)a.mask_stride;
     E = (double)slots * (double)c->cs.ne(a.g0);
@@ -76,15 +77,50 @@ static int pull_sync(nemo_ctx *c) {
     HIPCHK(c, hipEventSynchronize(c->ev_pull));
   }
   c->cs.pull_hint[c->cs.pull_which] = total;
-  if (!c->cs.pull_map.empty()) {  // shared regions: entry e takes its computed slot's (map[e] <= e)
+  if (c->cs.pull_expand) {  // shared regions: slot e takes its computed slot's (map[e] <= e)
     for (uint32_t e = c->cs.pull_slots; e-- > 0;) {
-      const uint32_t u = c->cs.pull_map[e];
+      const uint32_t u = c->cs.pull_expand[e];
       c->h_pull.off.p[e] = c->h_pull.off.p[u];
       c->h_pull.cnt.p[e] = c->h_pull.cnt.p[u];
     }
-    c->cs.pull_map.clear();
+    c->cs.pull_expand = nullptr;
   }
   c->cs.pull_synced = true;
+  return NEMO_OK;
+}
+
+// The slot list of a raw / simplified pull over the duplicate-graph classes (gdedup::pull_plan), made at the
+// first such pull after a load or a change of the pull's LDS tier and uploaded once.  The graphs past that
+// tier keep slots of their own: k_pull and k_mwp_* take duplicates like any graph, as the global tiers of the
+// other kernels do.  The tier is judged by the sizes, as everywhere on the host: a class inside the caps but
+// deeper than the tier's level cap shares a slot here and k_pull takes that one slot.  The big graphs' slots
+// follow the list on the device (PullArgs::big_slot: the chunk table keeps a row per big graph).
+// *use: some graph shares a slot (else the launches are the ones without classes).
+static int pull_plan(nemo_ctx *c, bool *use) {
+  CorpusState &s = c->cs;
+  const Tier &t = s.dc.t_pull;
+  if (!s.pl_ok || t.v != s.pl_tier.v || t.e != s.pl_tier.e || t.l != s.pl_tier.l || t.bytes != s.pl_tier.bytes) {
+    std::vector<uint8_t> apart(s.G);
+    for (uint32_t g = 0; g < s.G; g++)
+      apart[g] = !t.bytes || !tier_fits(t, (uint32_t)std::min<uint64_t>(s.nv(g), ~0u), (uint32_t)std::min<uint64_t>(s.ne(g), ~0u), 0);
+    s.pl = gdedup::pull_plan(s.gd_rep, apart);
+    s.pl_V = s.pl_E = 0;
+    for (uint32_t g : s.pl.list) s.pl_V += (double)s.nv(g), s.pl_E += (double)s.ne(g);
+    for (uint32_t g = 0; g < s.G; g++)
+      if (s.pl.map[g] > g) return fail(c, NEMO_ERR_STATE, "pull plan: graph %u's slot lies after it", g);
+    // a pull still reading the old list finishes first (a tier change is an option change: rare)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->aux) HIPCHK(c, hipStreamSynchronize(c->aux));
+    std::vector<uint32_t> up(s.pl.list);  // the list, then at G the big graphs' slots
+    up.resize(s.G);
+    for (uint32_t g : s.big_host) up.push_back(s.pl.map[g]);
+    if (int rc = s.d_pl_list.grow(c, (uint64_t)s.G + s.big_host.size())) return rc;
+    HIPCHK(c, hipMemcpyAsync(s.d_pl_list.p, up.data(), 4 * up.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s.pl_tier = t;
+    s.pl_ok = true;
+  }
+  *use = s.pl.list.size() < s.G;
   return NEMO_OK;
 }
 
@@ -111,7 +147,14 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
   // diff entries sharing a label source have one D mask, hence one graph: it is
   // compacted once and their slots share its region (pull_sync expands the table)
   const bool share = which == 2 && c->cs.n_uniq < c->cs.n_entries;
-  const uint32_t dslots = share ? c->cs.n_uniq : slots;
+  // graphs of identical content have one raw and one simplified edge list (node indices are graph-local):
+  // one graph per class is compacted and every graph of the class shares its region (pull_plan)
+  bool classes = which < 2 && c->cs.dc.dd_list && c->opt.pull_dedup;
+  if (classes && (rc = pull_plan(c, &classes))) return rc;
+  // which 0 / 1 over the classes compacts the listed graphs only, and those are representatives while the
+  // slices are stale (every graph inside the tier: device_load); which 2 reads run 0's post graph
+  if ((rc = which == 2 ? ensure_run0(c) : which < 2 && classes ? NEMO_OK : ensure_whole(c))) return rc;
+  const uint32_t dslots = share ? c->cs.n_uniq : classes ? (uint32_t)c->cs.pl.list.size() : slots;
   if ((rc = ensure_event(c, &c->ev_pull))) return rc;
   if ((rc = c->cs.d_pcur.grow(c, 1))) return rc;
   if (grow_slots) {
@@ -124,6 +167,7 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
   c->cs.pull_dslots = dslots;
   if (share) c->cs.pull_map = c->cs.dmap;
   else c->cs.pull_map.clear();
+  c->cs.pull_expand = share ? c->cs.pull_map.data() : classes ? c->cs.pl.map.data() : nullptr;
   if (slots == 0) return NEMO_OK;
   nemo::PullArgs a{};
   a.which = (uint32_t)which;
@@ -141,11 +185,11 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
     a.mask_off = c->cs.d_sdoff.p;
     cap = 0;  // S is an induced subgraph of the entry's graph
     for (uint32_t g : c->cs.sd_graph) cap += c->cs.ne(g);
-  } else if (which == 0) {
-    cap = c->cs.E;  // every edge
   } else {
-    // kept edges (<= E) + collapsed edges; a pull past the estimate re-runs on fetch
-    cap = std::max<uint64_t>(2 * c->cs.E + 1024, c->cs.pull_hint[1] + c->cs.pull_hint[1] / 4);
+    if (classes) a.slot_g = c->cs.d_pl_list.p, a.big_slot = c->cs.d_pl_list.p + c->cs.G;
+    const uint64_t E = classes ? (uint64_t)c->cs.pl_E : c->cs.E;  // of the graphs compacted
+    // which 0: every edge; which 1: kept edges (<= E) + collapsed edges; a pull past the estimate re-runs on fetch
+    cap = which == 0 ? E : std::max<uint64_t>(2 * E + 1024, c->cs.pull_hint[1] + c->cs.pull_hint[1] / 4);
   }
   a.cnt = c->cs.d_pcnt.p;
   a.off = c->cs.d_poff.p;
@@ -176,7 +220,7 @@ int nemo_pull_edges(nemo_ctx *c, int which) {
 uint64_t nemo_pulled_count(nemo_ctx *c, uint32_t slot) {
   DISPATCH(node_pulled_count(c, slot));
   if (!c || c->cs.pull_which < 0 || slot >= c->cs.pull_slots) return 0;
-  if (pull_sync(c)) return 0;
+  if (pull_sync(c)) return 0;  // no ensure_whole: reads the pull's slot table, no graph
   return c->h_pull.cnt.p[slot];
 }
 
@@ -186,6 +230,7 @@ int nemo_fetch_pulled(nemo_ctx *c, uint32_t slot, uint32_t *src, uint32_t *dst, 
   if (c->cs.pull_which < 0) return fail(c, NEMO_ERR_STATE, "nothing pulled");
   if (slot >= c->cs.pull_slots) return fail(c, NEMO_ERR_INVALID, "slot %u out of range", slot);
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: reads the pulled regions, no graph
   int rc = pull_sync(c);
   if (rc) return rc;
   const uint64_t a = c->h_pull.off.p[slot], n = c->h_pull.cnt.p[slot];
@@ -206,6 +251,7 @@ int nemo_fetch_pulled_all(nemo_ctx *c, uint64_t *off, uint32_t *cnt, uint32_t *s
   if (!c) return NEMO_ERR_INVALID;
   if (c->cs.pull_which < 0) return fail(c, NEMO_ERR_STATE, "nothing pulled");
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: reads the pulled regions, no graph
   int rc = pull_sync(c);
   if (rc) return rc;
   const uint64_t used = c->cs.pull_slots ? *c->h_pull.cur.p : 0;

@@ -9,6 +9,7 @@ int nemo_triggers(nemo_ctx *c) {
   if (!c->cs.marked) return fail(c, NEMO_ERR_STATE, "nemo_triggers before nemo_mark_holds");
   if (int rm = ensure_marked(c)) return rm;
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   c->cs.tcounts[0] = c->cs.tcounts[1] = c->cs.tcounts[2] = 0;
   c->cs.trig_done = true;
   c->cs.trig_pending = false;
@@ -60,6 +61,7 @@ int nemo_fetch_triggers(nemo_ctx *c, uint32_t *pre, uint64_t pre_cap, uint64_t *
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.trig_done) return fail(c, NEMO_ERR_STATE, "nemo_fetch_triggers before nemo_triggers");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_run0(c)) return rw;  // reads the build outputs of run 0's graphs only
   if (int rt = trig_sync(c)) return rt;
   if (n_pre) *n_pre = c->cs.tcounts[0];
   if (n_post) *n_post = c->cs.tcounts[1];
@@ -89,6 +91,7 @@ int nemo_fetch_node_flags(nemo_ctx *c, uint32_t g_lo, uint32_t g_hi, uint8_t *ou
   const uint64_t a = c->cs.node_off[g_lo], b = c->cs.node_off[g_hi];
   if (cap < b - a) return fail(c, NEMO_ERR_INVALID, "capacity too small");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   if (int rm = ensure_marked(c)) return rm;
   if (b > a) {
     HIPCHK(c, hipMemcpyAsync(out, c->cs.dc.flags + a, b - a, hipMemcpyDeviceToHost, c->stream));
@@ -102,6 +105,7 @@ int nemo_fetch_chains(nemo_ctx *c, nemo_chain *out, uint64_t cap, uint64_t *n_ou
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.simplified) return fail(c, NEMO_ERR_STATE, "no chains before nemo_simplify");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rw = ensure_whole(c)) return rw;  // may read any graph
   int rc;
   hipStream_t s = c->stream;
   if ((rc = c->cs.d_choff.grow(c, (uint64_t)c->cs.G + 1))) return rc;
@@ -182,6 +186,7 @@ int nemo_stage_simplified(nemo_ctx *c) {
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.simplified) return fail(c, NEMO_ERR_STATE, "nemo_stage_simplified before nemo_simplify");
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: the hand-over kernels read flags, nch and chain, which are replicated behind their kernels
   int rc;
   hipStream_t s = c->stream;
   if (!c->copy) {
@@ -244,6 +249,7 @@ int nemo_simplified_view(nemo_ctx *c, const uint8_t **state, const uint64_t **ch
   if (!c) return NEMO_ERR_INVALID;
   if (!c->cs.staged) return fail(c, NEMO_ERR_STATE, "nothing staged: call nemo_stage_simplified");
   HIPCHK(c, hipSetDevice(c->device));
+  // no ensure_whole: reads the staged flags and chain pairs, no build output
   HIPCHK(c, hipEventSynchronize(c->ev_copied));
   const uint64_t n = c->h_choff.p[c->cs.G];
   if (n > c->cs.staged_cap) {  // the hint was short: stage again at the real count

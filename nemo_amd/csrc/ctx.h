@@ -145,6 +145,9 @@ struct Options {
   int class_hash_bits = 128;  // nemo_diff_classes buckets by the low k bits of the hash (test knob: forces collisions)
   bool graph_dedup = true;    // option graph_dedup: the per-graph kernels run on one graph per distinct content
   int dedup_hash_bits = 128;  // the load's duplicate classes bucket by the low k bits of the hash (test knob)
+  bool proto_dedup = true;    // option proto_dedup: k_proto_lds runs on one run per run class (with graph_dedup)
+  bool replicate_lazy = true;  // option replicate_lazy: k_build's slices reach the duplicates when something reads them
+  bool pull_dedup = true;     // option pull_dedup: raw / simplified pulls compact one graph per class (with graph_dedup)
   uint32_t pair_hash_lds_max = LAB_HASH_LDS_SLOTS;  // largest label table (slots) k_lab_hash builds in LDS (0: none)
   uint32_t near_bits_lds_max = NEAR_LDS_MAX;  // largest bit row (bytes) k_near_bits builds in LDS (0: none)
   uint32_t near_ksplit = 0;                   // k_near_isect's K ranges (0: by the tile count and the device)
@@ -194,7 +197,24 @@ struct CorpusState : GraphSizes {
   uint32_t gd_nlist = 0, gd_npairs = 0, gd_classes = 0, gd_rounds = 0;
   uint32_t *d_gd_list = nullptr;     // [gd_nlist] the representatives
   uint32_t *d_gd_pairs = nullptr;    // [2 gd_npairs] (dup, rep) sorted by rep
+  uint32_t *d_gd_rep = nullptr;      // [G] gd_rep on the device (DevCorpus::dd_rep)
+  // k_build's slices of the duplicates (rp, rc, fp, fc, topo, lvl, nlv, e2, posoff) are not replicated yet:
+  // set by a load / rebuild that deferred them, cleared by ensure_whole
+  bool gd_stale = false;
   double gd_bytes[3] = {0, 0, 0};    // what a replicate pass writes per phase at most (timing table)
+  // ... and the run classes (runs whose pre graphs are of one class and whose post graphs are): dc.run_list
+  // is d_gd_rlist while dc.dd_list is set, the option proto_dedup is on and some run is a duplicate
+  uint32_t gd_nrlist = 0, gd_nrpairs = 0;
+  uint32_t *d_gd_rlist = nullptr;    // [gd_nrlist] the representative runs
+  uint32_t *d_gd_rpairs = nullptr;   // [2 gd_nrpairs] (dup, rep) sorted by rep
+  // ... and the raw / simplified pulls (option pull_dedup; gdedup::pull_plan): slot k of the launch is graph
+  // pl.list[k] (d_pl_list), and graph g's (offset, count) is slot pl.map[g]'s (<= g).  The graphs past the
+  // pull's LDS tier keep slots of their own, so the plan is made at the first pull under a tier (pl_tier)
+  gdedup::PullPlan pl;
+  Tier pl_tier{0, 0, 0, 0};
+  bool pl_ok = false;
+  DevBuf<uint32_t> d_pl_list;        // [G] the list | [n_big] the big graphs' slots
+  double pl_V = 0, pl_E = 0;         // nodes / edges of the listed graphs (k_pull's timer, the capacity)
 
   // diff: per-call buffers in whole 64-entry chunks.  d_dsrc, d_dmask, d_miss grow together; so do the
   // one-workgroup-per-entry kernels' scratch d_dbits, d_dumask, d_ddepth, d_dtopo
@@ -281,6 +301,9 @@ struct CorpusState : GraphSizes {
   uint32_t pull_slots = 0;
   uint32_t pull_dslots = 0;              // slots computed: diff entries sharing a label source share one
   std::vector<uint32_t> pull_map;        // which 2 with shared slots: entry -> computed slot
+  // the map pull_sync expands the slot tables by, once (null: none, or done): pull_map's, or pl.map's
+  // for a raw / simplified pull over one graph per class
+  const uint32_t *pull_expand = nullptr;
   DevBuf<uint32_t> d_pck;             // big graphs' pull chunk table
   DevBuf<uint32_t> d_pcnt;            // the slot tables: d_pcnt and d_poff grow together
   DevBuf<uint64_t> d_poff;
@@ -353,10 +376,11 @@ struct nemo_ctx {
   hipEvent_t ev_stage = nullptr;
   hipEvent_t ev_dclass = nullptr;  // nemo_diff_classes' hashes / verdicts have reached pinned memory
   hipEvent_t ev_near = nullptr;    // nemo_nearest_runs' label maximum / rows have reached pinned memory
-  hipEvent_t *const events[20] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_whole = nullptr;   // ensure_whole's replicate is queued on `stream`: `aux` waits for it
+  hipEvent_t *const events[21] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
-                                  &ev_dclass,  &ev_near};
+                                  &ev_dclass,  &ev_near,    &ev_whole};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -593,11 +617,39 @@ static inline int ensure_load_checked(nemo_ctx *c) {
   return rc;
 }
 
+// Duplicate graphs, option replicate_lazy (DESIGN.md §3 "Duplicate graphs"): a load / rebuild whose pass
+// is known to read the k_build slices of representatives only leaves the duplicates' slices stale.  Every
+// entry point calls this first, except the ones that state at their call site which graphs' build outputs
+// they read.  The replicate goes on `stream`; `aux`, where the diff kernels read graphs, waits for it.
+static inline int ensure_whole(nemo_ctx *c) {
+  if (!c->cs.gd_stale) return NEMO_OK;
+  int rc = timed(c, "k_replicate", c->cs.gd_bytes[GD_BUILD], 0, [&] {
+    nemo::launch_replicate(c->cs.dc, c->cs.d_gd_pairs, c->cs.gd_npairs, GD_BUILD_SLICES, c->stream);
+  });
+  if (rc) return rc;
+  c->cs.gd_stale = false;
+  if (c->aux) {
+    if ((rc = ensure_event(c, &c->ev_whole))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_whole, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_whole, 0));
+  }
+  return NEMO_OK;
+}
+// ... for the entry points that read run 0's graphs only: nothing to do while those are their own
+// representatives (run 0 need not be the first run)
+static inline int ensure_run0(nemo_ctx *c) {
+  if (!c->cs.gd_stale) return NEMO_OK;
+  const int32_t r = c->cs.run0;
+  if (r < 0 || (c->cs.gd_rep[2 * r] == 2u * r && c->cs.gd_rep[2 * r + 1] == 2u * r + 1u)) return NEMO_OK;
+  return ensure_whole(c);
+}
+
 // markConditionHolds is deferred for the LDS-tier graphs: nemo_simplify runs
 // it fused with the simplification (k_marksimp).  Anything that reads the
 // holds flags before that materialises it first (ensure_marked).
 static inline int ensure_marked(nemo_ctx *c) {
   if (!c->cs.mark_pending) return NEMO_OK;
+  if (int rw = ensure_whole(c)) return rw;  // k_mark walks every tier graph's rows
   const double V = c->cs.tierV, E = c->cs.tierE;
   int rc = timed(c, "k_mark", 8 * E + 13 * V, 2 * E, [&] { nemo::launch_mark(c->cs.dc, false, c->stream); });
   if (rc) return rc;

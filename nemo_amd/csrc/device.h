@@ -252,8 +252,16 @@ struct DevCorpus {
   // duplicates, or option graph_dedup 0).  k_build, k_marksimp and k_chains take graph dd_list[blockIdx.x]
   const uint32_t *dd_list;
   uint32_t dd_n;
+  const uint32_t *dd_rep;                // [G] graph -> its representative (set with dd_list)
   __device__ __forceinline__ uint32_t graph_of_block() const { return dd_list ? dd_list[blockIdx.x] : blockIdx.x; }
   __host__ uint32_t graph_blocks() const { return dd_list ? dd_n : G; }
+  // duplicate runs (gdedup_host.h run classes): the representative runs, ascending, and the (dup, rep)
+  // pairs; null = every run runs (dd_list null, no duplicate run, or option proto_dedup 0).  k_proto_lds
+  // takes run run_list[blockIdx.x] and k_proto_rep copies its rows to the duplicates
+  const uint32_t *run_list, *run_pairs;
+  uint32_t run_n, run_npairs;
+  __device__ __forceinline__ uint32_t run_of_block() const { return run_list ? run_list[blockIdx.x] : blockIdx.x; }
+  __host__ uint32_t run_blocks() const { return run_list ? run_n : n_runs; }
 
   __device__ __forceinline__ GraphView view(uint32_t g) const {
     GraphView v;

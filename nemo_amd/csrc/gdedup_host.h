@@ -52,4 +52,60 @@ static inline Plan plan(const std::vector<uint32_t> &rep, const std::vector<uint
   return p;
 }
 
+// A pull over one graph per class: slot k compacts graph list[k], and graph g is handed the region of
+// slot map[g].  A graph that is `apart` (the same for every graph of a class: it depends on the size
+// alone) keeps a slot of its own, as the graphs outside a kernel's tier do everywhere else; any other
+// takes its representative's.  map[g] <= g (a representative is the lowest graph of its class and the
+// list ascends), which is what an in-place expansion of the slot tables from the last graph down needs.
+struct PullPlan {
+  std::vector<uint32_t> list, map;
+};
+static inline PullPlan pull_plan(const std::vector<uint32_t> &rep, const std::vector<uint8_t> &apart) {
+  const uint32_t G = (uint32_t)rep.size();
+  PullPlan p;
+  p.map.resize(G);
+  std::vector<uint32_t> at(G, 0);
+  for (uint32_t g = 0; g < G; g++) {
+    if (rep[g] == g || apart[g]) {
+      at[g] = (uint32_t)p.list.size();
+      p.list.push_back(g);
+    }
+    p.map[g] = at[apart[g] ? g : rep[g]];
+  }
+  return p;
+}
+
+// Run classes: runs r and r' are of one class iff their pre graphs are of one graph class and their
+// post graphs are (rep[2r] == rep[2r'] and rep[2r + 1] == rep[2r' + 1]).  What a per-run kernel
+// computes from the two graphs alone (k_proto_lds) is then the same for both.
+struct RunPlan {
+  std::vector<uint32_t> rep;    // [n_runs] run -> the lowest-numbered run of its class
+  std::vector<uint32_t> list;   // the representative runs, ascending
+  std::vector<uint32_t> pairs;  // (dup, rep) per duplicate run, sorted by rep then dup
+};
+
+// rep: Plan::rep over the 2 n_runs graphs
+static inline RunPlan run_plan(const std::vector<uint32_t> &rep) {
+  const uint32_t n = (uint32_t)(rep.size() / 2);
+  RunPlan p;
+  p.rep.resize(n);
+  std::vector<std::pair<uint64_t, uint32_t>> key(n);  // ((pre class, post class), run)
+  for (uint32_t r = 0; r < n; r++) key[r] = {((uint64_t)rep[2 * r] << 32) | rep[2 * r + 1], r};
+  std::sort(key.begin(), key.end());
+  std::vector<std::pair<uint32_t, uint32_t>> v;  // (rep, dup)
+  for (uint32_t k = 0, first = 0; k < n; k++) {
+    if (key[k].first != key[first].first) first = k;
+    p.rep[key[k].second] = key[first].second;  // the lowest run of the key: runs ascend within a key
+    if (k != first) v.push_back({key[first].second, key[k].second});
+  }
+  for (uint32_t r = 0; r < n; r++)
+    if (p.rep[r] == r) p.list.push_back(r);
+  std::sort(v.begin(), v.end());
+  for (auto &x : v) {
+    p.pairs.push_back(x.second);
+    p.pairs.push_back(x.first);
+  }
+  return p;
+}
+
 }  // namespace gdedup

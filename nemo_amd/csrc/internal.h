@@ -178,7 +178,8 @@ struct DclassArgs {
 struct PullArgs {
   uint32_t which;           // 0 raw, 1 simplified, 2 diff, 3 symmetric diff
   uint32_t g0;              // graph of which == 2
-  const uint32_t *slot_g;   // which == 3: slot -> its graph (the entry's failed post graph)
+  const uint32_t *slot_g;   // which == 3: slot -> its graph (the entry's failed post graph); which 0 / 1: one graph
+                            // per duplicate-graph class (gdedup::pull_plan; null: slot g is graph g)
   const uint8_t *mask;      // which >= 2: D / S masks of the entries
   uint64_t mask_stride;     // which == 2: bytes between two entries' masks
   const uint64_t *mask_off; // which == 3: first mask byte of every slot (ragged masks)
@@ -192,6 +193,7 @@ struct PullArgs {
   // MWP_CH-node chunks, [row slots][maxck] chunk counts -> offsets (null: none)
   uint32_t *ccnt;
   uint32_t maxck;
+  const uint32_t *big_slot;  // which 0 / 1 with slot_g: slot of big graph DevCorpus::big[y] (chunk-table row y)
 };
 
 struct TrigArgs {
@@ -220,6 +222,8 @@ void launch_chains(const DevCorpus &c, hipStream_t s, bool tiers = true, const u
 #define GD_BUILD 0
 #define GD_MARKSIMP 1
 #define GD_CHAINS 2
+#define GD_BUILD_SCALARS 3  // GD_BUILD's per-graph scalars alone (redo, err, created, nlev)
+#define GD_BUILD_SLICES 4   // ... and its slices alone (ensure_whole, ctx.h)
 void launch_gd_hash(const DevCorpus &c, uint64_t *hash, hipStream_t s);
 void launch_gd_cmp(const DevCorpus &c, const uint32_t *pairs, uint32_t n_pairs, uint8_t *verdict, hipStream_t s);
 void launch_replicate(const DevCorpus &c, const uint32_t *pairs, uint32_t n_pairs, int phase, hipStream_t s);

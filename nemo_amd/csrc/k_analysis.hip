@@ -614,14 +614,17 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_pg_gate(DevCorpus c) {
 #define PB_RCHT 0x80u
 __global__ __launch_bounds__(PROTO_BLOCK) void k_proto_lds(DevCorpus c) {
   extern __shared__ __align__(16) uint8_t dyn[];
-  const uint32_t r = blockIdx.x;
+  const uint32_t r = c.run_of_block();
   const uint32_t g = 2 * r + 1;
   if (c.err[g] || c.err[g - 1]) return;
-  const GraphView gv = c.view(g);
+  // the post graph is read through its representative (same content, so the same flags, chains and
+  // Kahn order): a duplicate's k_build slices may be stale (ensure_whole, ctx.h)
+  const uint32_t gp = c.dd_rep ? c.dd_rep[g] : g;
+  const GraphView gv = c.view(gp);
   if (!proto_lds_fits(c, gv)) return;
   const uint32_t V = gv.V, E = gv.E, L = gv.nlev, W = c.words, tid = threadIdx.x;
   STAMP(0);
-  const uint32_t nch = c.nch[g];
+  const uint32_t nch = c.nch[gp];
   ProtoLds P = proto_carve(dyn, V, E, L, W, proto_chain_cap(V));
   uint32_t *s_s = P.words, *s_t = P.words + W;
   uint16_t *ab = P.ab;
@@ -755,6 +758,22 @@ __global__ __launch_bounds__(PROTO_BLOCK) void k_proto_lds(DevCorpus c) {
   STAMP(7);
 }
 
+// k_proto_lds ran on the representative runs (c.run_list): its rows to the duplicate runs, one
+// thread per pair.  A pair is copied only if k_proto_lds took the representative (its early
+// returns; their inputs are equal across a run class), so k_proto_sel lists a duplicate exactly
+// when it lists its representative and the global tier writes both.
+__global__ __launch_bounds__(NEMO_BLOCK) void k_proto_rep(DevCorpus c) {
+  const uint32_t k = blockIdx.x * NEMO_BLOCK + threadIdx.x;
+  if (k >= c.run_npairs) return;
+  const uint32_t d = c.run_pairs[2 * k], r = c.run_pairs[2 * k + 1], g = 2 * r + 1, W = c.words;
+  if (c.err[g] || c.err[g - 1] || !proto_lds_fits(c, c.view(g))) return;
+  for (uint32_t i = 0; i < W; i++) {
+    c.proto_bits[(size_t)d * W + i] = c.proto_bits[(size_t)r * W + i];
+    c.graph_tables[(size_t)d * W + i] = c.graph_tables[(size_t)r * W + i];
+  }
+  c.gate[d] = c.gate[r];
+}
+
 
 // markConditionHolds + cleanCopyProv + the local part of collapseNextChains
 // fused for the LDS-tier graphs, straight from the input edge list
@@ -867,7 +886,9 @@ void launch_marksimp(const DevCorpus &c, hipStream_t s, bool skip_built) {
 void launch_proto(const DevCorpus &c, hipStream_t s, bool tiers) {
   if (c.lds_bytes) {
     hipFuncSetAttribute((const void *)k_proto_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_bytes);
-    hipLaunchKernelGGL(k_proto_lds, dim3(c.n_runs), dim3(PROTO_BLOCK), c.lds_bytes, s, c);
+    hipLaunchKernelGGL(k_proto_lds, dim3(c.run_blocks()), dim3(PROTO_BLOCK), c.lds_bytes, s, c);
+    if (c.run_list)
+      hipLaunchKernelGGL(k_proto_rep, dim3((c.run_npairs + NEMO_BLOCK - 1) / NEMO_BLOCK), dim3(NEMO_BLOCK), 0, s, c);
   }
   if (!c.n_runs || !tiers) return;  // !tiers: the host knows the global tier's list is empty
   launch_zero(proto_list(c), sizeof(uint32_t), s);

@@ -585,11 +585,12 @@ __device__ __forceinline__ bool pull_alive(uint32_t which, const uint8_t *f, con
   if (which == 1) return (f[v] & (NEMO_F_KEPT | NEMO_F_DELETED)) == NEMO_F_KEPT;
   return m[v] != 0;
 }
-// graph and liveness mask of a pull slot: the slot's own graph (raw / simplified), run 0's post
-// graph with entry-major D masks (which 2), or the entry's failed post graph with ragged S masks
+// graph and liveness mask of a pull slot: the slot's own graph (raw / simplified; with a slot list,
+// the slot's representative graph: duplicates share its region on the host), run 0's post graph
+// with entry-major D masks (which 2), or the entry's failed post graph with ragged S masks
 // (which 3, the symmetric diff)
 __device__ __forceinline__ uint32_t pull_graph(const PullArgs &a, uint32_t slot) {
-  return a.which == 2 ? a.g0 : a.which == 3 ? a.slot_g[slot] : slot;
+  return a.which == 2 ? a.g0 : a.slot_g ? a.slot_g[slot] : slot;
 }
 __device__ __forceinline__ const uint8_t *pull_mask(const PullArgs &a, uint32_t slot) {
   if (!a.mask) return nullptr;
@@ -750,9 +751,10 @@ __device__ __forceinline__ bool mwp_slot(const DevCorpus &c, const PullArgs &a, 
   if (a.which >= 2) {
     s.slot = y;
     s.g = pull_graph(a, y);
-  } else {
+  } else {  // a row per big graph: a big graph is its own representative, in a slot of its own
     if (y >= c.n_big) return false;
-    s.g = s.slot = c.big[y];
+    s.g = c.big[y];
+    s.slot = a.big_slot ? a.big_slot[y] : s.g;
   }
   if (c.err[s.g]) return false;
   gv = c.view(s.g);
@@ -870,10 +872,11 @@ __global__ __launch_bounds__(MWP_BLOCK) void k_mwp_write(DevCorpus c, PullArgs a
 // Raw / simplified pulls: the graphs k_pull_lds leaves (errors, past the LDS
 // caps) are listed first, so k_pull runs a small grid over that list instead
 // of one mostly-empty workgroup per graph (~20k early exits cost ~38 us at C3).
-__global__ __launch_bounds__(NEMO_BLOCK) void k_pull_sel(DevCorpus c, uint32_t slots) {
-  const uint32_t g = blockIdx.x * NEMO_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(NEMO_BLOCK) void k_pull_sel(DevCorpus c, PullArgs a, uint32_t slots) {
+  const uint32_t slot = blockIdx.x * NEMO_BLOCK + threadIdx.x;
   bool need = false;
-  if (g < slots) {
+  if (slot < slots) {
+    const uint32_t g = pull_graph(a, slot);
     if (c.err[g]) {
       need = true;
     } else {
@@ -881,7 +884,7 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_pull_sel(DevCorpus c, uint32_t s
       need = !tier_fits(c.t_pull, gv.V, gv.E, gv.nlev);
     }
   }
-  wave_append(need, g, c.sel + 1, c.sel);
+  wave_append(need, slot, c.sel + 1, c.sel);
 }
 
 #define PULL_GRID 2048u
@@ -1064,11 +1067,11 @@ __global__ __launch_bounds__(PULL_BLOCK) void k_pull_lds(DevCorpus c, PullArgs a
 #define PULLR_BATCH 8
 __global__ __launch_bounds__(PULL_BLOCK) void k_pull_raw(DevCorpus c, PullArgs a) {
   __shared__ unsigned long long s_base;
-  const uint32_t g = blockIdx.x, tid = threadIdx.x;
+  const uint32_t slot = blockIdx.x, g = pull_graph(a, slot), tid = threadIdx.x;
   if (c.err[g]) {
     if (tid == 0) {
-      a.cnt[g] = 0;
-      a.off[g] = 0;
+      a.cnt[slot] = 0;
+      a.off[slot] = 0;
     }
     return;
   }
@@ -1078,8 +1081,8 @@ __global__ __launch_bounds__(PULL_BLOCK) void k_pull_raw(DevCorpus c, PullArgs a
   if (tid == 0) {
     const unsigned long long base = atomicAdd(a.cursor, (unsigned long long)E);
     s_base = base;
-    a.off[g] = base;
-    a.cnt[g] = E;
+    a.off[slot] = base;
+    a.cnt[slot] = E;
   }
   __syncthreads();
   const uint64_t base = s_base;
@@ -1376,7 +1379,7 @@ void launch_pull(const DevCorpus &c, const PullArgs &a, uint32_t slots, uint32_t
   if (!global) {
   } else if (a.which < 2) {
     launch_zero(c.sel, sizeof(uint32_t), s);
-    hipLaunchKernelGGL(k_pull_sel, dim3((slots + NEMO_BLOCK - 1) / NEMO_BLOCK), dim3(NEMO_BLOCK), 0, s, c, slots);
+    hipLaunchKernelGGL(k_pull_sel, dim3((slots + NEMO_BLOCK - 1) / NEMO_BLOCK), dim3(NEMO_BLOCK), 0, s, c, a, slots);
     grid = std::min(slots, PULL_GRID);
   }
   if (global) {

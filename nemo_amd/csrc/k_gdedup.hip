@@ -162,7 +162,9 @@ __device__ __forceinline__ void gd_copy(void *dst_, const void *src_, uint64_t n
   if (tid < tail) dst[16 * nc + tid] = src[16 * nc + tid];
 }
 
-// phase GD_BUILD: what k_build writes; GD_MARKSIMP: what k_marksimp (or k_build's tail) writes;
+// phase GD_BUILD: what k_build writes (GD_BUILD_SCALARS: its per-graph scalars alone, which the next
+// kernels read of every graph; GD_BUILD_SLICES: the rest, deferred until something reads a duplicate's
+// slices: ensure_whole, ctx.h); GD_MARKSIMP: what k_marksimp (or k_build's tail) writes;
 // GD_CHAINS: what the first chain tier writes.  A pair is copied under the condition its
 // representative's kernel ran under, so a class outside a kernel's tier is left to the per-graph
 // global kernels, which take duplicates like any other graph.
@@ -173,11 +175,11 @@ __global__ __launch_bounds__(GD_BLOCK) void k_replicate(DevCorpus c, const uint3
     const uint32_t d = pairs[2 * k], r = pairs[2 * k + 1];
     const uint64_t nd = c.node_off[d], nr = c.node_off[r], ed = c.edge_off[d], er = c.edge_off[r];
     const uint32_t V = (uint32_t)(c.node_off[r + 1] - nr), E = (uint32_t)(c.edge_off[r + 1] - er);
-    if (phase == GD_BUILD) {
+    if (phase == GD_BUILD || phase == GD_BUILD_SCALARS || phase == GD_BUILD_SLICES) {
       const bool built = c.bld_bytes != 0u && V <= c.bld_v && E <= c.bld_e;
       if (!built) continue;  // k_build returned at once: k_csr / k_topo take every graph of the class
       const uint32_t redo = c.redo[r], nl = min(c.nlev[r], V);
-      if (tid == 0) {
+      if (tid == 0 && phase != GD_BUILD_SLICES) {
         c.redo[d] = (uint8_t)redo;
         c.err[d] = c.err[r];
         if (!redo) {
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(GD_BLOCK) void k_replicate(DevCorpus c, const uint3
           c.nlev[d] = c.nlev[r];
         }
       }
-      if (redo) continue;  // handed to the global tier, duplicates included
+      if (redo || phase == GD_BUILD_SCALARS) continue;  // redo: handed to the global tier, duplicates included
       gd_copy(c.rp + nd + d, c.rp + nr + r, 4ull * (V + 1u));
       gd_copy(c.rc + ed, c.rc + er, 4ull * E);
       gd_copy(c.fp + nd + d, c.fp + nr + r, 4ull * (V + 1u));
