@@ -693,6 +693,126 @@ func (n *Neo4J) NearestRuns(queries, candidates []uint) ([]*NearestRun, error) {
 	return res, nil
 }
 
+// KnockOut is one hypothesis of a knock-out analysis: a set of nodes of one
+// provenance graph removed by assumption, and what that does to the graph read
+// as an AND/OR circuit (a goal holds if any of its rule firings holds, a rule
+// firing if all of its premises hold).
+type KnockOut struct {
+	Iteration uint   // the run
+	Cond      string // "pre" or "post"
+	Node      string // leaves mode: the ID of the sink goal knocked out; sets mode: ""
+	Label     string // ... and its label
+	Dead      uint   // dead nodes, the removed ones included
+	RootsDead uint   // dead nodes of in-degree 0
+	Roots     uint   // nodes of in-degree 0
+	Lost      bool   // every root is dead: the outcome has no derivation left
+}
+
+func condIndex(cond string) C.int {
+	if cond == "post" {
+		return 1
+	}
+	return 0
+}
+
+// knockRows fetches the rows of the last knock-out call.
+func (n *Neo4J) knockRows() ([]C.nemo_knock, error) {
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_knockout(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	rows := make([]C.nemo_knock, cnt+1)
+	if err := n.err(C.nemo_fetch_knockout(n.ctx, &rows[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	return rows[:cnt], nil
+}
+
+func (n *Neo4J) knockOut(k C.nemo_knock) *KnockOut {
+	p := n.graphs[int(k.graph)]
+	res := &KnockOut{Iteration: p.iter, Cond: p.cond, Dead: uint(k.n_dead), RootsDead: uint(k.roots_dead), Roots: uint(k.n_roots)}
+	res.Lost = k.n_roots > 0 && k.roots_dead == k.n_roots
+	if v := int(k.node); uint32(k.node) != ^uint32(0) && v < len(p.goals) {
+		res.Node, res.Label = p.goals[v].ID, p.goals[v].Label
+	}
+	return res
+}
+
+// KnockOutLeaves knocks out every sink goal (base fact) of the given runs'
+// pre or post provenance, one at a time (nemo_knockout_leaves), and returns
+// one record per sink goal, runs in list order.  It replaces the Cypher path
+// query "is there still a derivation of post if this event is lost?"; the
+// reference's graphing package has no counterpart.  The second result gives,
+// per listed run, the first record and the number of records of that run
+// (nemo_fetch_knockout_ranges).
+func (n *Neo4J) KnockOutLeaves(iters []uint, cond string) ([]*KnockOut, [][2]uint64, error) {
+	its := make([]C.uint32_t, len(iters)+1)
+	for i, it := range iters {
+		its[i] = C.uint32_t(it)
+	}
+	if err := n.err(C.nemo_knockout_leaves(n.ctx, &its[0], C.size_t(len(iters)), condIndex(cond), 0)); err != nil {
+		return nil, nil, err
+	}
+	rows, err := n.knockRows()
+	if err != nil {
+		return nil, nil, err
+	}
+	first, count := make([]C.uint64_t, len(iters)+1), make([]C.uint32_t, len(iters)+1)
+	if err := n.err(C.nemo_fetch_knockout_ranges(n.ctx, &first[0], &count[0], C.uint64_t(len(iters)))); err != nil {
+		return nil, nil, err
+	}
+	res := make([]*KnockOut, len(rows))
+	for h, k := range rows {
+		res[h] = n.knockOut(k)
+	}
+	ranges := make([][2]uint64, len(iters))
+	for i := range iters {
+		ranges[i] = [2]uint64{uint64(first[i]), uint64(count[i])}
+	}
+	return res, ranges, nil
+}
+
+// KnockOutSets evaluates explicit hypotheses on one run's pre or post
+// provenance (nemo_knockout_sets): sets[s] holds the local node indices
+// (goals first, then rules, in loading order) removed under hypothesis s.
+// With masks, the third result holds per hypothesis one byte per node,
+// 1 = dead (nemo_fetch_knockout_mask).
+func (n *Neo4J) KnockOutSets(iter uint, cond string, sets [][]uint32, masks bool) ([]*KnockOut, [][]byte, error) {
+	off := make([]C.uint64_t, len(sets)+1)
+	var nodes []C.uint32_t
+	for s, set := range sets {
+		for _, v := range set {
+			nodes = append(nodes, C.uint32_t(v))
+		}
+		off[s+1] = C.uint64_t(len(nodes))
+	}
+	nodes = append(nodes, 0) // never empty: &nodes[0] below
+	var flags C.uint32_t
+	if masks {
+		flags = C.NEMO_KO_MASKS
+	}
+	if err := n.err(C.nemo_knockout_sets(n.ctx, C.uint32_t(iter), condIndex(cond), &off[0], &nodes[0], C.size_t(len(sets)), flags)); err != nil {
+		return nil, nil, err
+	}
+	rows, err := n.knockRows()
+	if err != nil {
+		return nil, nil, err
+	}
+	res := make([]*KnockOut, len(rows))
+	var dead [][]byte
+	for h, k := range rows {
+		res[h] = n.knockOut(k)
+		if masks {
+			m := make([]byte, n.graphs[int(k.graph)].n()+1)
+			if err := n.err(C.nemo_fetch_knockout_mask(n.ctx, C.uint64_t(h), (*C.uint8_t)(unsafe.Pointer(&m[0])), C.uint64_t(len(m)))); err != nil {
+				return nil, nil, err
+			}
+			dead = append(dead, m[:len(m)-1])
+		}
+	}
+	return res, dead, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

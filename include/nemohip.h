@@ -240,7 +240,11 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       counts are split into, each range a workgroup per tile, summed
  *                       with integer atomics (0, default: one range unless the tiles
  *                       alone leave the device under two workgroups per CU; at most
- *                       1024 and the K-slabs of a row)                                */
+ *                       1024 and the K-slabs of a row)
+ *   "knock_lds_max"     largest LDS image (bytes) of a graph the knock-out sweep runs
+ *                       in LDS; graphs past it, and graphs of 65536 nodes or more, run
+ *                       the sweep over the CSR in device memory (default and upper
+ *                       bound 81920; 0 = every graph in device memory)                */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -473,6 +477,68 @@ int nemo_fetch_nearest(nemo_ctx *ctx, nemo_nearest *out, uint64_t cap, uint64_t 
  * positions, self-pairs with their true distance 0), copied from the device:
  * for callers that want the k nearest; cap >= (q_hi - q_lo) * n_c.             */
 int nemo_fetch_label_distances(nemo_ctx *ctx, uint32_t q_lo, uint32_t q_hi, uint32_t *out, uint64_t cap);
+
+/* ---- knock-out analysis: which events a run's outcome depends on ---------------
+ * A provenance graph is an AND/OR circuit: a goal holds if any of its rule
+ * firings holds, a rule firing holds if all of its premises hold.  The calls
+ * evaluate that circuit under many hypotheses at once; they replace the Cypher
+ * path query a Neo4j user could type ("is there still a derivation of post if
+ * this message is lost?") and restate on the device what Molly's own search
+ * walks.  The reference has no counterpart in its graphing package.
+ * The subject is a raw loaded graph g: run r's pre graph (cond 0) or post graph
+ * (cond 1), as loaded and not simplified; nemo_mark_holds is not needed.  A
+ * hypothesis h is a set F_h of nodes of g, removed by assumption.  dead_h(v) is
+ * defined bottom-up along the DUETO edges, sinks first:
+ *   - v in F_h: dead;
+ *   - v a rule (NEMO_NODE_RULE): dead iff at least one child is dead; a rule
+ *     without children is alive unless it is in F_h;
+ *   - v a goal with at least one child: dead iff all its children are dead;
+ *   - v a goal without children (a base fact): alive unless it is in F_h.
+ * The definition goes by the node's own kind only: it does not assume that goals
+ * and rules alternate.  Roots are the nodes of in-degree 0 (Kahn level 0).  For
+ * every hypothesis the call reports n_dead (dead nodes, F_h included),
+ * roots_dead and n_roots; the outcome is lost under h iff roots_dead == n_roots
+ * and n_roots > 0, and how to read that stays with the caller.  The empty set is
+ * a legal hypothesis (nothing is dead), a node named twice in a set counts once,
+ * a node index >= V_g is NEMO_ERR_INVALID.
+ * nemo_knockout_leaves makes one hypothesis per sink goal (a goal without
+ * children) of each listed run's graph, in node-index order within a graph,
+ * graphs in list order: hypothesis k of a graph knocks out its k-th sink goal.
+ * nemo_knockout_sets takes explicit hypotheses on one graph: set s is
+ * set_nodes[set_off[s] .. set_off[s+1]); set_off must not decrease
+ * (NEMO_ERR_INVALID otherwise).
+ * n == 0 or n_sets == 0 gives zero hypotheses and NEMO_OK; a graph with no sink
+ * goal contributes zero hypotheses; an iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; duplicate iterations give identical rows.  More than
+ * 2^32 - 2 hypotheses, dead words kept in device memory past 2^36 bytes (8 V_g
+ * bytes per chunk of 64 hypotheses: every chunk with NEMO_KO_MASKS, else only
+ * the chunks of graphs past the LDS tier), or sets naming more than 2^32 - 1
+ * nodes in all, are NEMO_ERR_LIMIT: tile the call.  Single-device contexts
+ * only (a node context returns NEMO_ERR_STATE).  Everything runs on the device
+ * on the context's stream; the calls block until the rows are on the host, as
+ * nemo_diff_classes does.  The results are the call's own state: valid until
+ * the next knock-out call or nemo_load_corpus (the fetches return
+ * NEMO_ERR_STATE otherwise), independent of the diff, symmetric diff, nearest
+ * and class state in both directions.                                          */
+typedef struct nemo_knock {
+  uint32_t graph;      /* 2r + cond                                                   */
+  uint32_t node;       /* leaves mode: the leaf knocked out (local index); sets mode: UINT32_MAX */
+  uint32_t n_dead;     /* dead nodes, F_h included                                    */
+  uint32_t roots_dead; /* dead nodes of in-degree 0                                   */
+  uint32_t n_roots;    /* nodes of in-degree 0                                        */
+} nemo_knock;
+#define NEMO_KO_MASKS 1u /* keep the dead masks for nemo_fetch_knockout_mask          */
+int nemo_knockout_leaves(nemo_ctx *ctx, const uint32_t *iters, size_t n, int cond, uint32_t flags);
+int nemo_knockout_sets(nemo_ctx *ctx, uint32_t iteration, int cond, const uint64_t *set_off, const uint32_t *set_nodes,
+                       size_t n_sets, uint32_t flags);
+/* out[h] for every hypothesis h; out == NULL queries *n_out.                    */
+int nemo_fetch_knockout(nemo_ctx *ctx, nemo_knock *out, uint64_t cap, uint64_t *n_out);
+/* Per listed graph (leaves mode: n entries) or the one graph (sets mode: one
+ * entry): its first hypothesis and how many it has; cap >= that many entries.  */
+int nemo_fetch_knockout_ranges(nemo_ctx *ctx, uint64_t *first, uint32_t *count, uint64_t cap);
+/* One byte per node of hypothesis hyp's graph, 1 = dead; cap >= V_g.  Needs a
+ * call with NEMO_KO_MASKS (NEMO_ERR_STATE otherwise).                           */
+int nemo_fetch_knockout_mask(nemo_ctx *ctx, uint64_t hyp, uint8_t *out, uint64_t cap);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

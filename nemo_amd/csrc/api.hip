@@ -327,6 +327,10 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.near_ksplit = value < 0 ? 0u : (uint32_t)std::min<int64_t>(value, NEAR_MAX_KSPLIT);
     return NEMO_OK;
   }
+  if (!strcmp(name, "knock_lds_max")) {  // largest LDS image (bytes) k_ko_lds takes; 0: every graph to k_ko_glob
+    c->opt.knock_lds_max = value < 0 ? KO_LDS_MAX : (uint32_t)std::min<int64_t>(value, KO_LDS_MAX);
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;

@@ -19,6 +19,7 @@
 #include "device.h"
 #include "gdedup_host.h"
 #include "internal.h"
+#include "knock_host.h"
 #include "nearest_host.h"
 #include "node.h"
 #include "pairs_host.h"
@@ -151,6 +152,7 @@ struct Options {
   uint32_t pair_hash_lds_max = LAB_HASH_LDS_SLOTS;  // largest label table (slots) k_lab_hash builds in LDS (0: none)
   uint32_t near_bits_lds_max = NEAR_LDS_MAX;  // largest bit row (bytes) k_near_bits builds in LDS (0: none)
   uint32_t near_ksplit = 0;                   // k_near_isect's K ranges (0: by the tile count and the device)
+  uint32_t knock_lds_max = KO_LDS_MAX;        // largest LDS image (bytes) k_ko_lds takes (0: every graph to k_ko_glob)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -295,6 +297,20 @@ struct CorpusState : GraphSizes {
   DevBuf<uint32_t> d_nrdesc;         // [rows] post graphs | [n_q] query rows | [n_c] candidate rows
   std::vector<uint32_t> nr_desc;     // the last call's upload
 
+  // knock-out (k_knock.hip): the call's own state, void after the next call or load; independent of every diff,
+  // nearest and class state.  d_kocnt grows alone, before the leaves are counted; the other five grow together
+  // once the hypotheses are known, in this order; all of it only inside the two calls
+  bool ko_done = false, ko_masks = false;
+  knock::Table ko_tab;               // the last call's chunk table and ranges
+  std::vector<uint32_t> ko_desc;     // the last leaves call's upload: [n] graphs | [n + 1] first hypotheses
+  std::vector<uint64_t> ko_setoff;   // the last sets call's upload: set offsets from the first set's
+  DevBuf<uint32_t> d_kocnt;          // [n] listed graphs | [n + 1] first hypotheses | [2 n] (leaves, Kahn levels)
+  DevBuf<uint32_t> d_koleaf;         // [hypotheses] the leaf of each (leaves mode) / the sets' nodes (sets mode)
+  DevBuf<knock::Chunk> d_kochunk;    // [chunks], then the two tiers' chunk lists (u32)
+  DevBuf<uint64_t> d_koset;          // [sets + 1] set offsets into d_koleaf (sets mode)
+  DevBuf<uint32_t> d_korows;         // [hypotheses][5] nemo_knock rows
+  DevBuf<uint64_t> d_kodead;         // dead words of the chunks that keep them (knock::Chunk::moff)
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -377,10 +393,11 @@ struct nemo_ctx {
   hipEvent_t ev_dclass = nullptr;  // nemo_diff_classes' hashes / verdicts have reached pinned memory
   hipEvent_t ev_near = nullptr;    // nemo_nearest_runs' label maximum / rows have reached pinned memory
   hipEvent_t ev_whole = nullptr;   // ensure_whole's replicate is queued on `stream`: `aux` waits for it
-  hipEvent_t *const events[21] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_knock = nullptr;   // the knock-out calls' counts / rows have reached pinned memory
+  hipEvent_t *const events[22] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
-                                  &ev_dclass,  &ev_near,    &ev_whole};
+                                  &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -392,11 +409,12 @@ struct nemo_ctx {
   // nemo_diff_classes: h_dcin uploads (entry counts, pairs), h_dcout receives (hashes, |D|, support, verdicts)
   Pinned<uint32_t> h_dcin, h_dcout;
   Pinned<uint32_t> h_near;  // nemo_nearest_runs: [n_q][4] rows, then the label maximum
-  void **const pinned[22] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint32_t> h_knock;  // the knock-out calls: the listed graphs' (leaves, Kahn levels), then the rows
+  void **const pinned[23] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
-                             h_dcin.slot(),  h_dcout.slot(),   h_near.slot()};
+                             h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

@@ -162,6 +162,27 @@ struct NearArgs {
   uint32_t *out;              // [n_q][4] nemo_nearest rows: cand, dist, only_query, only_cand
 };
 
+// One nemo_knockout_leaves / nemo_knockout_sets call (k_knock.hip): hypotheses in chunks of 64 per graph
+// (knock_host.h Chunk, passed as raw 32-byte rows), one bit column per hypothesis in a u64 dead word per node.
+struct KnockArgs {
+  const uint32_t *list;     // leaves mode: [n_list] the listed graphs
+  const uint32_t *loff;     // leaves mode: [n_list + 1] first hypothesis of each list position
+  uint32_t *cnt;            // leaves mode: [n_list][2] sink goals and Kahn levels of each listed graph (k_ko_leaves)
+  uint32_t n_list;
+  const uint4 *chunk;       // [chunks][2] the chunk table
+  const uint32_t *sel;      // the launched tier's chunk indices
+  uint32_t *leaf;           // leaves mode: [hypotheses] the sink goal of each; sets mode: the sets' nodes
+  const uint64_t *set_off;  // sets mode: [sets + 1] offsets into leaf (null: leaves mode)
+  uint64_t *dead;           // dead words of the chunks that keep them
+  uint32_t *rows;           // [hypotheses][5] nemo_knock
+  uint32_t masks;           // 1: every chunk stores its dead words at its moff
+};
+// k_ko_leaves: write false counts (a.cnt), true lists the sink goals at a.loff (a.leaf)
+void launch_ko_leaves(const DevCorpus &c, const KnockArgs &a, bool write, hipStream_t s);
+// a.sel: n chunk indices of one tier; lds_bytes: the largest image among them (k_ko_lds's dynamic LDS)
+void launch_ko_lds(const DevCorpus &c, const KnockArgs &a, uint32_t n, uint32_t lds_bytes, hipStream_t s);
+void launch_ko_glob(const DevCorpus &c, const KnockArgs &a, uint32_t n, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

@@ -38,6 +38,10 @@ class CTiming(ctypes.Structure):
 
 # struct nemo_nearest (nemo_fetch_nearest)
 NEAREST_DTYPE = np.dtype([("cand", np.uint32), ("dist", np.uint32), ("only_query", np.uint32), ("only_cand", np.uint32)])
+# struct nemo_knock (nemo_fetch_knockout)
+KNOCK_DTYPE = np.dtype([("graph", np.uint32), ("node", np.uint32), ("n_dead", np.uint32), ("roots_dead", np.uint32),
+                        ("n_roots", np.uint32)])
+KO_MASKS = 1  # NEMO_KO_MASKS
 
 
 def header_symbols() -> List[str]:
@@ -108,6 +112,11 @@ def lib():
             "nemo_nearest_runs": ([vp, vp, sz, vp, sz], i32),
             "nemo_fetch_nearest": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_label_distances": ([vp, u32, u32, vp, u64], i32),
+            "nemo_knockout_leaves": ([vp, vp, sz, i32, u32], i32),
+            "nemo_knockout_sets": ([vp, u32, i32, vp, vp, sz, u32], i32),
+            "nemo_fetch_knockout": ([vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_knockout_ranges": ([vp, vp, vp, u64], i32),
+            "nemo_fetch_knockout_mask": ([vp, u64, vp, u64], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -319,6 +328,60 @@ class Engine:
         q_hi = n_q if q_hi is None else q_hi
         out = np.zeros((max(q_hi - q_lo, 0), n_c), np.uint32)
         self._chk(self.L.nemo_fetch_label_distances(self.h, q_lo, q_hi, _p(out), out.size))
+        return out
+
+    def knockout_leaves(self, iters: Sequence[int], cond: int = 1, masks: bool = False) -> np.ndarray:
+        """nemo_knockout_leaves: one hypothesis per sink goal (a goal without children) of every listed run's
+        pre (cond 0) or post (cond 1) graph, knocked out alone.  Returns the rows as a structured array
+        (KNOCK_DTYPE: graph, node, n_dead, roots_dead, n_roots), graphs in list order, a graph's sink goals in
+        node-index order; knockout_ranges() locates each listed graph's rows.  masks: keep the dead masks for
+        knockout_mask()."""
+        it = np.ascontiguousarray(iters, dtype=np.uint32)
+        self._ko_ranges = 0
+        self._chk(self.L.nemo_knockout_leaves(self.h, _p(it), len(it), int(cond), KO_MASKS if masks else 0))
+        self._ko_ranges = len(it)
+        return self.knockout_rows()
+
+    def knockout_sets(self, iteration: int, cond: int, sets: Sequence[Sequence[int]], masks: bool = False) -> np.ndarray:
+        """nemo_knockout_sets: explicit hypotheses on one graph, each a set of local node indices removed by
+        assumption (the empty set is legal).  Returns one KNOCK_DTYPE row per set (node = UINT32_MAX)."""
+        off = np.zeros(len(sets) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in sets], dtype=np.uint64)
+        nodes = np.ascontiguousarray([v for x in sets for v in x], dtype=np.uint32)
+        return self.knockout_sets_raw(iteration, cond, off, nodes, len(sets), masks)
+
+    def knockout_sets_raw(self, iteration: int, cond: int, set_off: np.ndarray, set_nodes: np.ndarray, n_sets: int,
+                          masks: bool = False) -> np.ndarray:
+        """nemo_knockout_sets with the caller's own offsets (u64 [n_sets + 1]) and node array (u32)."""
+        off = np.ascontiguousarray(set_off, dtype=np.uint64)
+        nodes = np.ascontiguousarray(set_nodes, dtype=np.uint32)
+        self._ko_ranges = 0
+        self._chk(self.L.nemo_knockout_sets(self.h, int(iteration), int(cond), off.ctypes.data, _p(nodes), int(n_sets),
+                                            KO_MASKS if masks else 0))
+        self._ko_ranges = 1 if n_sets else 0
+        return self.knockout_rows()
+
+    def knockout_rows(self) -> np.ndarray:
+        """nemo_fetch_knockout: the rows of the last knock-out call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_knockout(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, KNOCK_DTYPE)
+        self._chk(self.L.nemo_fetch_knockout(self.h, _p(out), len(out), ctypes.byref(n)))
+        return out
+
+    def knockout_ranges(self):
+        """nemo_fetch_knockout_ranges: (first hypothesis u64, count u32) per listed graph of the last leaves
+        call, or of the one graph of the last sets call."""
+        n = getattr(self, "_ko_ranges", 0)
+        first, count = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+        self._chk(self.L.nemo_fetch_knockout_ranges(self.h, _p(first), _p(count), n))
+        return first, count
+
+    def knockout_mask(self, hyp: int, n_nodes: int) -> np.ndarray:
+        """nemo_fetch_knockout_mask: one byte per node of hypothesis `hyp`'s graph (n_nodes of them), 1 = dead;
+        needs a call with masks=True."""
+        out = np.zeros(n_nodes, np.uint8)
+        self._chk(self.L.nemo_fetch_knockout_mask(self.h, int(hyp), _p(out), len(out)))
         return out
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:

@@ -429,6 +429,19 @@ class Neo4J:
                  "OnlyNearest": None if int(r["cand"]) == none else int(r["only_cand"])}
                 for q, r in zip(queries, rows)]
 
+    def CriticalLeaves(self, run: int, cond: str = "post") -> List[Tuple[str, str]]:
+        """The base facts the run's outcome depends on one by one: (node ID, label) of every sink goal
+        of the run's raw pre / post provenance whose single loss leaves no root of the graph with a
+        derivation (nemo_knockout_leaves: the graph as an AND/OR circuit, a goal holds if any of its
+        rule firings holds, a rule firing if all of its premises hold; lost means roots_dead ==
+        n_roots > 0).  It has no reference counterpart: with Neo4j a user typed a Cypher path query
+        per event.  The strings stay on the host; the device returns node indices."""
+        c = self.Runs
+        n0 = int(c.node_off[self._g(int(run), cond)])
+        rows = self.eng.knockout_leaves([int(run)], 0 if cond == "pre" else 1)
+        return [(c.node_ids[n0 + int(r["node"])], c.labels[int(c.label[n0 + int(r["node"])])])
+                for r in rows if int(r["n_roots"]) > 0 and int(r["roots_dead"]) == int(r["n_roots"])]
+
     def _surplus_dots(self, failedRuns: Sequence[int]):
         """(marked DOTs, surplus events) of the last symmetric / pairs call, whose entries walked the
         post graphs of failedRuns."""
