@@ -813,6 +813,66 @@ func (n *Neo4J) KnockOutSets(iter uint, cond string, sets [][]uint32, masks bool
 	return res, dead, nil
 }
 
+// MinCut is one minimal cut of a run's provenance: a smallest set of nodes
+// whose joint loss leaves no root of the graph with a derivation, while the
+// loss of any proper subset does not.
+type MinCut struct {
+	Nodes  []uint32 // local node indices, in candidate-list order
+	IDs    []string // their node IDs ("" for a rule)
+	Labels []string // ... and labels
+}
+
+// MinCuts returns all minimal cuts of at most maxSize (1..3) nodes of one
+// run's pre or post provenance among the candidates (nemo_min_cuts): local
+// node indices of any kind, or nil for every sink goal (base fact) of the
+// graph.  It answers "this run survives the loss of any one message; which
+// pairs or triples of losses break it?", the question lineage-driven fault
+// injection searches; the reference's graphing package has no counterpart.
+// The cuts come sorted by size, then by the colex rank of their positions in
+// the list of candidates that are no cut alone.  The second result holds, per
+// size 1..3, the live candidates entering the round, the hypotheses evaluated
+// and the minimal cuts found (nemo_fetch_min_cut_stats).
+func (n *Neo4J) MinCuts(iter uint, cond string, candidates []uint32, maxSize uint) ([]*MinCut, [9]uint64, error) {
+	var stats [9]uint64
+	var list *C.uint32_t
+	if candidates != nil {
+		nodes := make([]C.uint32_t, len(candidates)+1) // never empty: &nodes[0] below
+		for i, v := range candidates {
+			nodes[i] = C.uint32_t(v)
+		}
+		list = &nodes[0]
+	}
+	if err := n.err(C.nemo_min_cuts(n.ctx, C.uint32_t(iter), condIndex(cond), list, C.size_t(len(candidates)), C.uint32_t(maxSize), 0)); err != nil {
+		return nil, stats, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_min_cuts(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	cuts := make([]C.nemo_cut, cnt+1)
+	if err := n.err(C.nemo_fetch_min_cuts(n.ctx, &cuts[0], cnt, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	if err := n.err(C.nemo_fetch_min_cut_stats(n.ctx, (*C.uint64_t)(unsafe.Pointer(&stats[0])))); err != nil {
+		return nil, stats, err
+	}
+	p := n.graphs[2*n.runIdx[iter]+int(condIndex(cond))]
+	res := make([]*MinCut, cnt)
+	for k, cut := range cuts[:cnt] {
+		m := &MinCut{}
+		for j := 0; j < int(cut.size); j++ {
+			v := uint32(cut.node[j])
+			id, label := "", ""
+			if int(v) < len(p.goals) {
+				id, label = p.goals[v].ID, p.goals[v].Label
+			}
+			m.Nodes, m.IDs, m.Labels = append(m.Nodes, v), append(m.IDs, id), append(m.Labels, label)
+		}
+		res[k] = m
+	}
+	return res, stats, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

@@ -244,7 +244,12 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *   "knock_lds_max"     largest LDS image (bytes) of a graph the knock-out sweep runs
  *                       in LDS; graphs past it, and graphs of 65536 nodes or more, run
  *                       the sweep over the CSR in device memory (default and upper
- *                       bound 81920; 0 = every graph in device memory)                */
+ *                       bound 81920; 0 = every graph in device memory); nemo_min_cuts
+ *                       takes its tier from the same option
+ *   "cut_grid"          most workgroups of nemo_min_cuts' persistent sweeps (0, default:
+ *                       as many as are resident on the device, at most one per chunk
+ *                       of 64 hypotheses); a test knob: 1 makes one workgroup take
+ *                       every chunk                                                   */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -539,6 +544,53 @@ int nemo_fetch_knockout_ranges(nemo_ctx *ctx, uint64_t *first, uint32_t *count, 
 /* One byte per node of hypothesis hyp's graph, 1 = dead; cap >= V_g.  Needs a
  * call with NEMO_KO_MASKS (NEMO_ERR_STATE otherwise).                           */
 int nemo_fetch_knockout_mask(nemo_ctx *ctx, uint64_t hyp, uint8_t *out, uint64_t cap);
+
+/* ---- minimal cut sets: the smallest fault sets that defeat a run's outcome ------
+ * The subject (a raw loaded graph g = 2r + cond), dead_F(v), the roots and "the
+ * outcome is lost under F" (roots_dead == n_roots > 0) are the knock-out
+ * definitions above.  nemo_min_cuts searches where nemo_knockout_sets evaluates:
+ * the caller names candidates, the device makes the hypotheses itself.
+ * Candidates: cand[0 .. n_cand) are graph-local node indices of any kind (goals,
+ * rules, inner nodes); cand == NULL means every sink goal of the graph in
+ * node-index order (the list nemo_knockout_leaves makes).  A node >= V_g, or a
+ * node listed twice, is NEMO_ERR_INVALID, checked on the host before anything is
+ * uploaded.
+ * A cut is a set F of candidates under which the outcome is lost; it is minimal
+ * if no proper subset of it is a cut.  dead is monotone in F, so every superset
+ * of a cut is a cut.  The call returns all minimal cuts of size <= max_size;
+ * max_size must be 1, 2 or 3 and flags 0 (NEMO_ERR_INVALID otherwise).
+ * Rounds: round 1 evaluates the K singletons; the candidates that are no cut by
+ * themselves form the live list, in candidate order, K1 entries.  Round 2
+ * evaluates all C(K1,2) pairs of live positions; every lost pair is minimal.
+ * Round 3 evaluates all C(K1,3) triples; a lost triple is minimal iff none of
+ * its three pairs was lost in round 2.  A round with fewer live candidates than
+ * its size has zero hypotheses.
+ * Hypothesis index: live positions a < b < c have the colex rank
+ * C(c,3) + C(b,2) + a, pairs C(b,2) + a, singles a; hypothesis h of round s is
+ * the set of rank h.  The rows are sorted by (size, rank): the order is
+ * deterministic.  A row's nodes are node indices in candidate-list order,
+ * unused entries UINT32_MAX.
+ * More than 2^32 - 2 hypotheses in one round is NEMO_ERR_LIMIT (shorten the
+ * candidate list); the call then leaves no results.  K1 is known after round 1
+ * only, so a call may run round 1 before it reports the limit.  n_cand == 0
+ * with a list, a graph without roots, and a graph with no cut up to max_size
+ * give zero rows and NEMO_OK.  An iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; a node context returns NEMO_ERR_STATE.  The call blocks
+ * until the rows are on the host, as the knock-out calls do.  The results are
+ * the call's own state: valid until the next nemo_min_cuts or nemo_load_corpus
+ * (the fetches return NEMO_ERR_STATE otherwise), independent of the knock-out,
+ * diff, symmetric diff, nearest and class state in both directions.            */
+typedef struct nemo_cut {
+  uint32_t size;    /* 1..3                                                          */
+  uint32_t node[3]; /* nodes in candidate-list order, unused = UINT32_MAX            */
+} nemo_cut;
+int nemo_min_cuts(nemo_ctx *ctx, uint32_t iteration, int cond, const uint32_t *cand, size_t n_cand, uint32_t max_size,
+                  uint32_t flags);
+/* out[k] for every minimal cut k; out == NULL queries *n_out.                  */
+int nemo_fetch_min_cuts(nemo_ctx *ctx, nemo_cut *out, uint64_t cap, uint64_t *n_out);
+/* Per size s = 1..3, out[3 (s - 1) ..]: live candidates entering the round,
+ * hypotheses evaluated, minimal cuts found (zeros for s > max_size).           */
+int nemo_fetch_min_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

@@ -331,6 +331,10 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.knock_lds_max = value < 0 ? KO_LDS_MAX : (uint32_t)std::min<int64_t>(value, KO_LDS_MAX);
     return NEMO_OK;
   }
+  if (!strcmp(name, "cut_grid")) {  // most workgroups of the cut-set sweeps; 0 / -1: as many as are resident
+    c->opt.cut_grid = value < 0 ? 0u : (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF);
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;

@@ -15,6 +15,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "cut_host.h"
 #include "dclass_host.h"
 #include "device.h"
 #include "gdedup_host.h"
@@ -153,6 +154,7 @@ struct Options {
   uint32_t near_bits_lds_max = NEAR_LDS_MAX;  // largest bit row (bytes) k_near_bits builds in LDS (0: none)
   uint32_t near_ksplit = 0;                   // k_near_isect's K ranges (0: by the tile count and the device)
   uint32_t knock_lds_max = KO_LDS_MAX;        // largest LDS image (bytes) k_ko_lds takes (0: every graph to k_ko_glob)
+  uint32_t cut_grid = 0;                      // test knob: most workgroups of k_cut_lds / k_cut_glob (0: as many as are resident)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -311,6 +313,25 @@ struct CorpusState : GraphSizes {
   DevBuf<uint32_t> d_korows;         // [hypotheses][5] nemo_knock rows
   DevBuf<uint64_t> d_kodead;         // dead words of the chunks that keep them (knock::Chunk::moff)
 
+  // minimal cut sets (k_cuts.hip): the call's own state, void after the next nemo_min_cuts or load; independent of
+  // knock-out, diff, nearest and class state.  All of it grows only inside nemo_min_cuts, each buffer to the largest
+  // request so far, behind a wait for the stream: d_cutdesc alone, before anything is counted; d_cutcand, d_cutlive,
+  // d_cutw[0] and d_cutdead together once the candidates are known, in this order; d_cutw[1], d_cutw[2] and
+  // d_cutscan together once round 1 has left the live list; d_cutrows alone once the totals are known
+  bool cut_done = false;
+  uint64_t cut_rows = 0;             // rows of the last call (in nemo_ctx::h_cuts)
+  uint64_t cut_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size: live candidates, hypotheses, minimal cuts
+  uint32_t cut_up[4] = {0, 0, 0, 0};  // the last call's uploads to d_cutdesc
+  std::vector<uint32_t> cut_cand;    // the last call's candidates (nodes)
+  std::vector<uint32_t> cut_live;    // ... and its upload: [K1] live positions | [K1] their nodes
+  DevBuf<uint32_t> d_cutdesc;        // [8] k_ko_leaves' list, offsets and counts for the one graph (cand == NULL)
+  DevBuf<uint32_t> d_cutcand;        // [K] candidate position -> node
+  DevBuf<uint32_t> d_cutlive;        // [K] live position -> candidate position | [K] live position -> node
+  DevBuf<uint64_t> d_cutw[3];        // the rounds' words, one per chunk of 64 ranks
+  DevBuf<uint64_t> d_cutdead;        // k_cut_glob: dead words of every workgroup of the launch
+  DevBuf<uint32_t> d_cutscan;        // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
+  DevBuf<uint32_t> d_cutrows;        // [rows][4] nemo_cut
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -394,10 +415,12 @@ struct nemo_ctx {
   hipEvent_t ev_near = nullptr;    // nemo_nearest_runs' label maximum / rows have reached pinned memory
   hipEvent_t ev_whole = nullptr;   // ensure_whole's replicate is queued on `stream`: `aux` waits for it
   hipEvent_t ev_knock = nullptr;   // the knock-out calls' counts / rows have reached pinned memory
-  hipEvent_t *const events[22] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_cuts = nullptr;    // nemo_min_cuts' counts / words / totals / rows have reached pinned memory
+  hipEvent_t *const events[23] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
-                                  &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock};
+                                  &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
+                                  &ev_cuts};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -410,11 +433,13 @@ struct nemo_ctx {
   Pinned<uint32_t> h_dcin, h_dcout;
   Pinned<uint32_t> h_near;  // nemo_nearest_runs: [n_q][4] rows, then the label maximum
   Pinned<uint32_t> h_knock;  // the knock-out calls: the listed graphs' (leaves, Kahn levels), then the rows
-  void **const pinned[23] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint32_t> h_cuts;   // nemo_min_cuts: counts, round 1's words and the candidates, the totals, then the rows
+  void **const pinned[24] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
-                             h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot()};
+                             h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
+                             h_cuts.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

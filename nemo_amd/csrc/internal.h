@@ -183,6 +183,28 @@ void launch_ko_leaves(const DevCorpus &c, const KnockArgs &a, bool write, hipStr
 void launch_ko_lds(const DevCorpus &c, const KnockArgs &a, uint32_t n, uint32_t lds_bytes, hipStream_t s);
 void launch_ko_glob(const DevCorpus &c, const KnockArgs &a, uint32_t n, hipStream_t s);
 
+// One round of nemo_min_cuts (k_cuts.hip): the hypotheses of the round are the sets of `size` live positions,
+// in colex rank order (cut_host.h), 64 consecutive ranks per chunk, one u64 result word per chunk.
+struct CutArgs {
+  uint32_t graph;           // 2r + cond
+  uint32_t size;            // 1..3: the round
+  uint32_t n_hyp, n_chunks;
+  const uint32_t *cand;     // [K] candidate position -> node
+  const uint32_t *live;     // [K1] live position -> candidate position (null in round 1: every candidate is live)
+  const uint32_t *lnode;    // [K1] live position -> node: cand[live[p]], as the sweeps read it
+  uint64_t *words;          // [n_chunks] bit t of word k: hypothesis 64 k + t is a minimal cut
+  const uint64_t *pairs;    // round 3: round 2's words (a lost pair is a minimal one: bit C(y,2) + x)
+  uint64_t *dead;           // k_cut_glob: [workgroups][dead_words(V)]
+  uint32_t *scan;           // [n_chunks + 1] popcounts of the words, then their exclusive scan; [n_chunks] = total
+  uint32_t *rows;           // k_cut_emit: the round's first nemo_cut row (4 u32 each)
+};
+// the workgroups of round `size`'s k_cut_lds resident on the device at lds_bytes of dynamic LDS (0: the query failed)
+uint32_t cut_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu);
+void launch_cut_lds(const DevCorpus &c, const CutArgs &a, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void launch_cut_glob(const DevCorpus &c, const CutArgs &a, uint32_t grid, hipStream_t s);
+void launch_cut_count(const CutArgs &a, hipStream_t s);  // a.scan[k] = popcount(a.words[k]), a.scan[n_chunks] = 0
+void launch_cut_emit(const CutArgs &a, hipStream_t s);   // the rows of the round's set bits at a.rows, by a.scan
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

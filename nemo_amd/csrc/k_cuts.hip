@@ -1,0 +1,146 @@
+// k_cuts.hip — nemo_min_cuts (DESIGN.md §Minimal cut sets): all minimal cuts of size <= 3 of a raw provenance
+// graph read as an AND/OR circuit.  A round's hypotheses are the sets of 1, 2 or 3 live candidates in colex rank
+// order (cut_host.h), so a workgroup makes the seeds of a chunk of 64 hypotheses from the chunk's index alone.
+// k_cut_lds is the persistent form of k_ko_lds: it stages the graph's LDS image once and loops over chunks,
+// running the knock-out sweep (ko_sweep.h) on each; a chunk's result is one word, the AND of the root words.
+// k_cut_glob is the same loop over the CSR in device memory.  k_cut_count / k_cut_emit turn the rounds' words
+// into nemo_cut rows in (size, rank) order.
+#include "cut_host.h"
+#include "device.h"
+#include "internal.h"
+#include "ko_sweep.h"
+
+namespace nemo {
+
+// All chunks ci = blockIdx.x, += gridDim.x of the round on a graph whose image is in place.  All 256 threads.
+template <bool LDS, uint32_t SIZE>
+__device__ __forceinline__ void cut_loop(const CutArgs &a, const KoImg<LDS> &g) {
+  __shared__ uint64_t s_and[KO_BLOCK / 64];
+  const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+  uint64_t *dead = g.dead;
+  uint4 *z = reinterpret_cast<uint4 *>(dead);
+  const uint32_t pairs = (g.V + 1u) / 2u;
+  for (uint32_t ci = blockIdx.x; ci < a.n_chunks; ci += gridDim.x) {
+    // the previous chunk's words go (its last reads lie behind the barrier that ends the loop body)
+    for (uint32_t i = tid; i < pairs; i += KO_BLOCK) z[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (!LDS) __threadfence_block();
+    __syncthreads();
+    const uint32_t first = ci * KO_CHUNK, n = min(KO_CHUNK, a.n_hyp - first);
+    // seeds: lane t's hypothesis is the set of rank first + t; hypotheses of one chunk share nodes
+    bool sub = false;  // round 3: one of the set's pairs is a cut already
+    if (tid < n) {
+      const uint64_t h = (uint64_t)first + tid, bit = 1ull << tid;
+      const cuts::Pos p = cuts::unrank<SIZE>(h);  // the round is a template parameter: no divergent unrank paths
+      unsigned long long *d64 = reinterpret_cast<unsigned long long *>(dead);
+      const uint32_t va = a.lnode[p.a], vb = SIZE >= 2u ? a.lnode[p.b] : g.V, vc = SIZE >= 3u ? a.lnode[p.c] : g.V;
+      if (va < g.V) atomicOr(&d64[va], (unsigned long long)bit);
+      if (SIZE >= 2u && vb < g.V) atomicOr(&d64[vb], (unsigned long long)bit);
+      if (SIZE >= 3u && vc < g.V) atomicOr(&d64[vc], (unsigned long long)bit);
+      if (SIZE == 3u) {  // the three pairs' bits of round 2's words, read while the sweep runs
+        const uint64_t r0 = cuts::rank2(p.a, p.b), r1 = cuts::rank2(p.a, p.c), r2 = cuts::rank2(p.b, p.c);
+        const uint64_t w0 = a.pairs[r0 >> 6], w1 = a.pairs[r1 >> 6], w2 = a.pairs[r2 >> 6];
+        sub = (((w0 >> (r0 & 63u)) | (w1 >> (r1 & 63u)) | (w2 >> (r2 & 63u))) & 1ull) != 0ull;
+      }
+    }
+    if (!LDS) __threadfence_block();
+    __syncthreads();
+    ko_sweep<LDS>(g);
+    // lost: every root dead, per bit column (the level offsets are staged: read behind a barrier)
+    const uint32_t n_roots = g.L ? (uint32_t)g.lvl[1] : 0u;
+    uint64_t w = ~0ull;
+    for (uint32_t i = tid; i < n_roots; i += KO_BLOCK) w &= dead[g.topo[i]];
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) w &= (uint64_t)__shfl_xor((unsigned long long)w, dd);
+    if (lane == 0) s_and[wave] = w;
+    __syncthreads();
+    if (wave == 0) {
+      uint64_t lost = n_roots ? (s_and[0] & s_and[1] & s_and[2] & s_and[3]) : 0ull;
+      lost &= n == KO_CHUNK ? ~0ull : (1ull << n) - 1ull;
+      if (SIZE == 3u) lost &= ~__ballot(sub);
+      if (lane == 0) a.words[ci] = lost;
+    }
+  }
+}
+
+// one instantiation per round (SIZE = 1, 2, 3)
+template <uint32_t SIZE>
+__global__ __launch_bounds__(KO_BLOCK) void k_cut_lds(DevCorpus c, CutArgs a) {
+  extern __shared__ __align__(16) uint8_t dyn[];
+  const GraphView gv = c.view(a.graph);
+  const KoImg<true> g = ko_stage_image(gv, dyn);  // once; the loop's first barrier ends the staging
+  cut_loop<true, SIZE>(a, g);
+}
+
+// the workgroup's own dead words in a.dead; a fence and a barrier per level, as k_ko_glob.  Correct, not tuned.
+template <uint32_t SIZE>
+__global__ __launch_bounds__(KO_BLOCK) void k_cut_glob(DevCorpus c, CutArgs a) {
+  const GraphView gv = c.view(a.graph);
+  KoImg<false> g;
+  g.fp = gv.fp, g.fc = gv.fc, g.topo = gv.topo, g.lvl = gv.lvl, g.rule = nullptr, g.word = gv.word;
+  g.dead = a.dead + (uint64_t)blockIdx.x * (((uint64_t)gv.V + 1ull) & ~1ull);
+  g.V = gv.V, g.L = gv.nlev;
+  cut_loop<false, SIZE>(a, g);
+}
+
+// ---- the rows -------------------------------------------------------------------------------------
+__global__ __launch_bounds__(KO_BLOCK) void k_cut_count(CutArgs a) {
+  const uint32_t k = blockIdx.x * KO_BLOCK + threadIdx.x;
+  if (k < a.n_chunks) a.scan[k] = (uint32_t)__popcll(a.words[k]);
+  if (k == a.n_chunks) a.scan[k] = 0u;
+}
+
+// A wave per word, a lane per bit: a set bit's row is the word's first row (the scan) plus the set bits below it.
+__global__ __launch_bounds__(KO_BLOCK) void k_cut_emit(CutArgs a) {
+  const uint32_t k = blockIdx.x * (KO_BLOCK / 64) + (threadIdx.x >> 6), lane = lane_id();
+  if (k >= a.n_chunks) return;
+  const uint64_t w = a.words[k];
+  if (!((w >> lane) & 1ull)) return;
+  const uint64_t h = (uint64_t)k * KO_CHUNK + lane;
+  const cuts::Pos p = a.size == 1u ? cuts::unrank<1>(h) : a.size == 2u ? cuts::unrank<2>(h) : cuts::unrank<3>(h);
+  const uint64_t r = (uint64_t)a.scan[k] + (uint32_t)__popcll(w & ((1ull << lane) - 1ull));
+  uint4 row = make_uint4(a.size, NEMO_NONE, NEMO_NONE, NEMO_NONE);
+  row.y = a.cand[a.live ? a.live[p.a] : p.a];  // live position -> candidate -> node (round 1: every candidate is live)
+  if (a.size >= 2u) row.z = a.cand[a.live[p.b]];
+  if (a.size >= 3u) row.w = a.cand[a.live[p.c]];
+  reinterpret_cast<uint4 *>(a.rows)[r] = row;
+}
+
+static const void *cut_lds_kernel(uint32_t size) {
+  return size == 1u ? (const void *)k_cut_lds<1> : size == 2u ? (const void *)k_cut_lds<2> : (const void *)k_cut_lds<3>;
+}
+
+uint32_t cut_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu) {
+  int per_cu = 0;
+  const void *f = cut_lds_kernel(size);
+  if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, KO_BLOCK, lds_bytes) != hipSuccess || per_cu < 1) {
+    (void)hipGetLastError();
+    return 0u;
+  }
+  return (uint32_t)per_cu * n_cu;
+}
+
+void launch_cut_lds(const DevCorpus &c, const CutArgs &a, uint32_t grid, uint32_t lds_bytes, hipStream_t s) {
+  if (!a.n_chunks) return;
+  if (a.size == 1u) hipLaunchKernelGGL(k_cut_lds<1>, dim3(grid), dim3(KO_BLOCK), lds_bytes, s, c, a);
+  else if (a.size == 2u) hipLaunchKernelGGL(k_cut_lds<2>, dim3(grid), dim3(KO_BLOCK), lds_bytes, s, c, a);
+  else hipLaunchKernelGGL(k_cut_lds<3>, dim3(grid), dim3(KO_BLOCK), lds_bytes, s, c, a);
+}
+
+void launch_cut_glob(const DevCorpus &c, const CutArgs &a, uint32_t grid, hipStream_t s) {
+  if (!a.n_chunks) return;
+  if (a.size == 1u) hipLaunchKernelGGL(k_cut_glob<1>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
+  else if (a.size == 2u) hipLaunchKernelGGL(k_cut_glob<2>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
+  else hipLaunchKernelGGL(k_cut_glob<3>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
+}
+
+void launch_cut_count(const CutArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_cut_count, dim3(a.n_chunks / KO_BLOCK + 1u), dim3(KO_BLOCK), 0, s, a);
+}
+
+void launch_cut_emit(const CutArgs &a, hipStream_t s) {
+  if (!a.n_chunks) return;
+  hipLaunchKernelGGL(k_cut_emit, dim3((a.n_chunks + KO_BLOCK / 64 - 1u) / (KO_BLOCK / 64)), dim3(KO_BLOCK), 0, s, a);
+}
+
+}  // namespace nemo

@@ -4,17 +4,12 @@
 // each node's (OR for a rule, AND for a goal with children) in pull form: no atomics in the sweep, one barrier
 // per level.  k_ko_leaves lists the sink goals (leaves mode), k_ko_lds sweeps a graph staged in LDS, k_ko_glob
 // the same over the CSR in device memory.
-#include <type_traits>
-
 #include "device.h"
 #include "internal.h"
 #include "knock_host.h"
+#include "ko_sweep.h"
 
 namespace nemo {
-
-#define KO_BLOCK 256
-#define KO_Q 4      // 16-byte chunks of node words per thread and round: 16 consecutive nodes
-#define KO_HUB 32u  // a row of more children than this is folded by the whole wave
 
 struct KoChunk {
   uint32_t graph, first, n;
@@ -126,21 +121,7 @@ void launch_ko_leaves(const DevCorpus &c, const KnockArgs &a, bool write, hipStr
   hipLaunchKernelGGL(k_ko_leaves, dim3(a.n_list), dim3(KO_BLOCK), 0, s, c, a, write ? 1u : 0u);
 }
 
-// ---- the sweep -----------------------------------------------------------------------------------
-// The graph as the sweep reads it: u16 arrays in LDS (k_ko_lds) or the u32 CSR in device memory (k_ko_glob).
-template <bool LDS>
-struct KoImg {
-  using idx = typename std::conditional<LDS, uint16_t, uint32_t>::type;
-  const idx *fp, *fc, *topo, *lvl;
-  const uint64_t *rule;  // LDS: a bit per node
-  const uint32_t *word;  // else the node words
-  uint64_t *dead;        // [V] (whole 16-byte pairs)
-  uint32_t V, L;
-  __device__ __forceinline__ bool is_rule_node(uint32_t v) const {
-    return LDS ? ((rule[v >> 6] >> (v & 63u)) & 1ull) != 0ull : is_rule(word[v]);
-  }
-};
-
+// ---- the sweep (KoImg, ko_stage_image and ko_sweep: ko_sweep.h) ------------------------------------
 // lane b's return value: how many of the wave's 64 words have bit b set (a ballot per bit column)
 __device__ __forceinline__ uint32_t ko_colcount(uint64_t w) {
   if (__ballot(w != 0ull) == 0ull) return 0u;
@@ -182,43 +163,7 @@ __device__ __forceinline__ void ko_run(const KnockArgs &a, const KoChunk &k, con
   }
   if (!LDS) __threadfence_block();
   __syncthreads();
-  // levels nlev-1 .. 0: a node's children lie on strictly deeper levels, so their words are final
-  for (int l = (int)g.L - 1; l >= 0; l--) {
-    const uint32_t lo = g.lvl[l], hi = g.lvl[l + 1];
-    for (uint32_t base = lo; base < hi; base += KO_BLOCK) {
-      const uint32_t i = base + tid;
-      const bool act = i < hi;
-      const uint32_t v = act ? (uint32_t)g.topo[i] : 0u;
-      const uint32_t b = act ? (uint32_t)g.fp[v] : 0u, e = act ? (uint32_t)g.fp[v + 1u] : 0u;
-      const bool rule = act && g.is_rule_node(v);
-      const bool hub = e - b > KO_HUB;
-      uint64_t acc = (rule || e == b) ? 0ull : ~0ull;
-      if (!hub)
-        for (uint32_t j = b; j < e; j++) {
-          const uint64_t w = dead[g.fc[j]];
-          acc = rule ? acc | w : acc & w;
-        }
-      for (uint64_t hm = __ballot(hub); hm; hm &= hm - 1ull) {  // wave-uniform: one long row at a time
-        const int src = __ffsll((long long)hm) - 1;
-        const uint32_t hb = (uint32_t)__shfl((int)b, src), he = (uint32_t)__shfl((int)e, src);
-        const bool hr = __shfl((int)rule, src) != 0;
-        uint64_t part = hr ? 0ull : ~0ull;
-        for (uint32_t j = hb + lane; j < he; j += 64u) {
-          const uint64_t w = dead[g.fc[j]];
-          part = hr ? part | w : part & w;
-        }
-#pragma unroll
-        for (int dd = 32; dd >= 1; dd >>= 1) {
-          const uint64_t y = (uint64_t)__shfl_xor((unsigned long long)part, dd);
-          part = hr ? part | y : part & y;
-        }
-        if ((int)lane == src) acc = part;
-      }
-      if (act) dead[v] |= acc;  // the seed stays
-    }
-    if (!LDS) __threadfence_block();  // the level's words in device memory before the next level reads them
-    __syncthreads();
-  }
+  ko_sweep<LDS>(g);
   // per bit column: dead nodes, and dead nodes of level 0
   const uint32_t n_roots = g.L ? (uint32_t)g.lvl[1] : 0u;
   uint32_t cd = 0, cr = 0;
@@ -253,43 +198,14 @@ __device__ __forceinline__ void ko_run(const KnockArgs &a, const KoChunk &k, con
 // u16, a rule bit per node (knock_lds_bytes): a level step never goes to device memory.
 __global__ __launch_bounds__(KO_BLOCK) void k_ko_lds(DevCorpus c, KnockArgs a) {
   extern __shared__ __align__(16) uint8_t dyn[];
-  const uint32_t tid = threadIdx.x, lane = lane_id();
+  const uint32_t tid = threadIdx.x;
   const KoChunk k = ko_chunk(a, a.sel[blockIdx.x]);
   const GraphView gv = c.view(k.graph);
-  const uint32_t V = gv.V, E = gv.E, L = gv.nlev;
-  uint8_t *p = dyn;
-  uint64_t *dead = reinterpret_cast<uint64_t *>(p);
-  p += knock::ko_align(8u * V);
-  uint16_t *fp = reinterpret_cast<uint16_t *>(p);
-  p += knock::ko_align(2u * (V + 1u));
-  uint16_t *fc = reinterpret_cast<uint16_t *>(p);
-  p += knock::ko_align(2u * E);
-  uint16_t *topo = reinterpret_cast<uint16_t *>(p);
-  p += knock::ko_align(2u * V);
-  uint16_t *lvl = reinterpret_cast<uint16_t *>(p);
-  p += knock::ko_align(2u * (L + 1u));
-  uint64_t *rule = reinterpret_cast<uint64_t *>(p);
-  // the rule bits from the node words: every load of a round before the first ballot
-  for (uint32_t base = 0; base < V; base += KO_Q * KO_BLOCK) {
-    uint32_t w[KO_Q];
-#pragma unroll
-    for (int q = 0; q < KO_Q; q++) w[q] = gv.word[min(base + q * KO_BLOCK + tid, V - 1u)];
-#pragma unroll
-    for (int q = 0; q < KO_Q; q++) {
-      const uint32_t v = base + q * KO_BLOCK + tid;
-      const uint64_t m = __ballot(v < V && is_rule(w[q]));
-      if (lane == 0 && v < V) rule[v >> 6] = m;
-    }
-  }
-  const StageDesc d[4] = {{gv.fp, fp, V + 1u, ST_U16}, {gv.fc, fc, E, ST_U16}, {gv.topo, topo, V, ST_U16},
-                          {gv.lvl, lvl, L + 1u, ST_U16}};
-  stage_lds<4, KO_BLOCK>(d);
-  uint4 *z = reinterpret_cast<uint4 *>(dead);
-  const uint32_t pairs = (V + 1u) / 2u;
+  const KoImg<true> g = ko_stage_image(gv, dyn);
+  uint4 *z = reinterpret_cast<uint4 *>(g.dead);
+  const uint32_t pairs = (gv.V + 1u) / 2u;
   for (uint32_t i = tid; i < pairs; i += KO_BLOCK) z[i] = make_uint4(0u, 0u, 0u, 0u);
   __syncthreads();
-  KoImg<true> g;
-  g.fp = fp, g.fc = fc, g.topo = topo, g.lvl = lvl, g.rule = rule, g.word = nullptr, g.dead = dead, g.V = V, g.L = L;
   ko_run<true>(a, k, g);
   if (a.masks) {  // the V words out in 16-byte stores (ko_run ends behind a barrier)
     uint4 *o = reinterpret_cast<uint4 *>(a.dead + k.moff);

@@ -42,6 +42,8 @@ NEAREST_DTYPE = np.dtype([("cand", np.uint32), ("dist", np.uint32), ("only_query
 KNOCK_DTYPE = np.dtype([("graph", np.uint32), ("node", np.uint32), ("n_dead", np.uint32), ("roots_dead", np.uint32),
                         ("n_roots", np.uint32)])
 KO_MASKS = 1  # NEMO_KO_MASKS
+# struct nemo_cut (nemo_fetch_min_cuts)
+CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (3,))])
 
 
 def header_symbols() -> List[str]:
@@ -117,6 +119,9 @@ def lib():
             "nemo_fetch_knockout": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_knockout_ranges": ([vp, vp, vp, u64], i32),
             "nemo_fetch_knockout_mask": ([vp, u64, vp, u64], i32),
+            "nemo_min_cuts": ([vp, u32, i32, vp, sz, u32, u32], i32),
+            "nemo_fetch_min_cuts": ([vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_min_cut_stats": ([vp, vp], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -383,6 +388,34 @@ class Engine:
         out = np.zeros(n_nodes, np.uint8)
         self._chk(self.L.nemo_fetch_knockout_mask(self.h, int(hyp), _p(out), len(out)))
         return out
+
+    def min_cuts(self, iteration: int, cond: int, candidates: Optional[Sequence[int]] = None, max_size: int = 2) -> np.ndarray:
+        """nemo_min_cuts: all minimal cuts of size <= max_size (1..3) of a run's pre (cond 0) or post (cond 1) graph
+        among `candidates` (graph-local node indices of any kind; None: every sink goal in node-index order).
+        Returns the rows as a structured array (CUT_DTYPE: size, node[3] in candidate-list order, unused entries
+        UINT32_MAX), sorted by (size, colex rank of the live positions); min_cut_stats() has the rounds' counts."""
+        if candidates is None:
+            self._chk(self.L.nemo_min_cuts(self.h, int(iteration), int(cond), None, 0, int(max_size), 0))
+        else:
+            cand = np.ascontiguousarray(candidates, dtype=np.uint32)
+            keep = cand if len(cand) else np.zeros(1, np.uint32)  # an empty list is a list: never NULL
+            self._chk(self.L.nemo_min_cuts(self.h, int(iteration), int(cond), _p(keep), len(cand), int(max_size), 0))
+        return self.min_cut_rows()
+
+    def min_cut_rows(self) -> np.ndarray:
+        """nemo_fetch_min_cuts: the rows of the last min_cuts call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_min_cuts(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, CUT_DTYPE)
+        self._chk(self.L.nemo_fetch_min_cuts(self.h, _p(out), len(out), ctypes.byref(n)))
+        return out
+
+    def min_cut_stats(self) -> np.ndarray:
+        """nemo_fetch_min_cut_stats: a 3 x 3 u64 array, row s - 1 = (live candidates entering round s, hypotheses
+        evaluated, minimal cuts found)."""
+        out = np.zeros(9, np.uint64)
+        self._chk(self.L.nemo_fetch_min_cut_stats(self.h, _p(out)))
+        return out.reshape(3, 3)
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
         """nemo_goal_labels: [n, label...] of a run's goal labels into device memory."""
