@@ -716,7 +716,12 @@ int nemo_timings(nemo_ctx *ctx, nemo_timing *out, uint32_t cap, uint32_t *n_out)
 int nemo_reset_timings(nemo_ctx *ctx);
 int nemo_synchronize(nemo_ctx *ctx);
 /* Inspection hook for tests: copy bytes of a named internal device array
- * ("topo", "lvl", "nlev", "fp", "fc", "rp", "rc", "flags", "dbits", "dmask"). */
+ * ("topo", "lvl", "nlev", "fp", "fc", "rp", "rc", "flags", "dbits", "dmask",
+ * "e2", "posoff").  "e2" (one u32 per edge, at the graph's edge offset: src <<
+ * 16 | dst, graph-local node indices, the forward rows in the Kahn order of
+ * their source) and "posoff" (one u32 per node, at the graph's node offset:
+ * the first e2 entry of each Kahn position) hold the post graphs that the LDS
+ * tier of the load built; the entries of every other graph are unspecified. */
 int nemo_debug_copy(nemo_ctx *ctx, const char *name, void *out, uint64_t offset, uint64_t bytes);
 
 #ifdef __cplusplus

@@ -1303,6 +1303,8 @@ int nemo_debug_copy(nemo_ctx *c, const char *name, void *out, uint64_t offset, u
   else if (n == "fc") base = c->cs.dc.fc;
   else if (n == "rp") base = c->cs.dc.rp;
   else if (n == "rc") base = c->cs.dc.rc;
+  else if (n == "e2") base = c->cs.dc.e2;  // (entries of graphs k_build did not build: unspecified)
+  else if (n == "posoff") base = c->cs.dc.posoff;
   else if (n == "flags") base = c->cs.dc.flags;
   else if (n == "dbits") base = c->cs.d_dbits.p;
   else if (n == "dmask") base = c->cs.d_dmask.p;

@@ -15,6 +15,7 @@ from nemo_amd import engine as E
 from nemo_amd.corpus import DIFF_PER_RUN, DIFF_REFERENCE, corpus_from_graphs
 from oracle import oracle as O
 from tests.compare import assert_same
+from tests.load_reference import created as _created
 
 pytestmark = pytest.mark.gpu
 
@@ -148,16 +149,6 @@ def _inject(corpus, g, extra):
     corpus.edge_dst = np.concatenate([corpus.edge_dst[:b], ys, corpus.edge_dst[b:]])
     eo[g + 1:] += len(extra)
     corpus.edge_off = eo.astype(np.uint64)
-
-
-def _created(corpus, g):
-    """pre-post-prov.go:150-210's relationships-created count: distinct edges joining a goal and a rule."""
-    import numpy as np
-    from nemo_amd.corpus import NODE_RULE
-    eo, no = corpus.edge_off.astype(np.int64), corpus.node_off.astype(np.int64)
-    rule = (corpus.node_word[no[g]:no[g + 1]] & NODE_RULE) != 0
-    pairs = set(zip(corpus.edge_src[eo[g]:eo[g + 1]].tolist(), corpus.edge_dst[eo[g]:eo[g + 1]].tolist()))
-    return sum(1 for x, y in pairs if rule[x] != rule[y]), int(eo[g + 1] - eo[g])
 
 
 @pytest.mark.parametrize("case", ["short_rows", "wide_row", "long_row", "hbm_bucket"])
