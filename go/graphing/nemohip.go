@@ -873,6 +873,68 @@ func (n *Neo4J) MinCuts(iter uint, cond string, candidates []uint32, maxSize uin
 	return res, stats, nil
 }
 
+// LabelKnockOut is the result of KnockoutLabels: one bit per (listed run, set).
+type LabelKnockOut struct {
+	Chunks int        // words per listed run: ceil(sets / 64)
+	Lost   [][]uint64 // [run][chunk]: bit s%64 of word s/64 = the run's outcome is lost under set s
+	Hit    [][]uint64 // ... = set s names a label some node of the run's graph carries
+	NLost  []uint32   // per set: the listed runs it breaks (a run listed twice counts twice)
+	NHit   []uint32   // per set: the listed runs it touches
+}
+
+// KnockoutLabels tests fault sets against every listed run's pre or post
+// provenance in one call (nemo_knockout_labels).  A set names interned labels:
+// "the message clock(a, b, 3, 4) is lost" is the same event in every run, so
+// the same set stands for it on every graph.  A set removes every node whose
+// label it names (sinksOnly: every base fact); the run's outcome is lost if no
+// root of its graph keeps a derivation.  It answers "in which other good runs
+// are run 0's cuts cuts too?" and "which single event breaks the most runs?"
+// without translating labels to node indices per run; the reference's graphing
+// package has no counterpart.
+func (n *Neo4J) KnockoutLabels(iters []uint, cond string, sets [][]uint32, sinksOnly bool) (*LabelKnockOut, error) {
+	its := make([]C.uint32_t, len(iters)+1)
+	for i, it := range iters {
+		its[i] = C.uint32_t(it)
+	}
+	off := make([]C.uint64_t, len(sets)+1)
+	var labels []C.uint32_t
+	for s, set := range sets {
+		for _, l := range set {
+			labels = append(labels, C.uint32_t(l))
+		}
+		off[s+1] = C.uint64_t(len(labels))
+	}
+	labels = append(labels, 0) // never empty: &labels[0] below
+	var flags C.uint32_t
+	if sinksOnly {
+		flags = C.NEMO_KL_SINKS
+	}
+	if err := n.err(C.nemo_knockout_labels(n.ctx, &its[0], C.size_t(len(iters)), condIndex(cond), &off[0], &labels[0], C.size_t(len(sets)), flags)); err != nil {
+		return nil, err
+	}
+	res := &LabelKnockOut{Chunks: (len(sets) + 63) / 64}
+	words := len(iters) * res.Chunks
+	lost, hit := make([]C.uint64_t, words+1), make([]C.uint64_t, words+1)
+	if err := n.err(C.nemo_fetch_knockout_labels(n.ctx, &lost[0], &hit[0], C.uint64_t(words))); err != nil {
+		return nil, err
+	}
+	nLost, nHit := make([]C.uint32_t, len(sets)+1), make([]C.uint32_t, len(sets)+1)
+	if err := n.err(C.nemo_fetch_knockout_label_counts(n.ctx, &nLost[0], &nHit[0], C.uint64_t(len(sets)))); err != nil {
+		return nil, err
+	}
+	for i := range iters {
+		l, h := make([]uint64, res.Chunks), make([]uint64, res.Chunks)
+		for c := 0; c < res.Chunks; c++ {
+			l[c], h[c] = uint64(lost[i*res.Chunks+c]), uint64(hit[i*res.Chunks+c])
+		}
+		res.Lost, res.Hit = append(res.Lost, l), append(res.Hit, h)
+	}
+	for s := range sets {
+		res.NLost, res.NHit = append(res.NLost, uint32(nLost[s])), append(res.NHit, uint32(nHit[s]))
+	}
+	return res, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

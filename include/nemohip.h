@@ -249,7 +249,17 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *   "cut_grid"          most workgroups of nemo_min_cuts' persistent sweeps (0, default:
  *                       as many as are resident on the device, at most one per chunk
  *                       of 64 hypotheses); a test knob: 1 makes one workgroup take
- *                       every chunk                                                   */
+ *                       every chunk
+ *   "kl_grid"           most workgroups of nemo_knockout_labels' persistent sweeps (0,
+ *                       default: as many as are resident on the device); the twin of
+ *                       "cut_grid", a test knob: 1 makes one workgroup walk every
+ *                       listed graph in turn, small values split a graph's chunks
+ *                       into few ranges; the tier is "knock_lds_max"'s
+ *   "kl_hitlist"        1 (default, also -1): the LDS-tier sweep of nemo_knockout_labels
+ *                       lists, once per graph, the nodes whose label some set names,
+ *                       and a chunk of 64 sets probes its table with those alone.  0:
+ *                       no list, every chunk probes with every node's label (same
+ *                       results; the form the list was measured against, tested)    */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -591,6 +601,47 @@ int nemo_fetch_min_cuts(nemo_ctx *ctx, nemo_cut *out, uint64_t cap, uint64_t *n_
 /* Per size s = 1..3, out[3 (s - 1) ..]: live candidates entering the round,
  * hypotheses evaluated, minimal cuts found (zeros for s > max_size).           */
 int nemo_fetch_min_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
+
+/* ---- knock-out by label: fault sets tested against every listed run in one call ----
+ * The subject (a raw loaded graph), dead_F(v), the roots and "the outcome is lost
+ * under F" (roots_dead == n_roots > 0) are the knock-out definitions above.  A
+ * hypothesis here names events, not nodes: an interned label is the same event
+ * in every run of the corpus.  Set s names the labels
+ * set_labels[set_off[s] .. set_off[s+1]).  On the graph of list position i,
+ * g = 2 * run_index(iters[i]) + cond, set s removes F(i,s): every node of g, goal
+ * or rule, whose label is in the set.  Under NEMO_KL_SINKS only sink goals match:
+ * nodes that are no rule and have no children (an empty forward row).
+ * The result is a bit per (list position, set), in chunks of 64 sets:
+ * n_chunks = ceil(n_sets / 64), set s is bit s & 63 of word [i * n_chunks + s / 64].
+ *   lost bit (i,s): roots_dead == n_roots > 0 under F(i,s);
+ *   hit bit (i,s):  F(i,s) is non-empty.
+ * Bits of the last chunk at or past n_sets are 0.  n_lost[s] and n_hit[s] count
+ * list positions: a run listed twice counts twice, and its two rows of words are
+ * identical.  An empty set hits nothing and loses nothing; a label named twice
+ * in a set counts once; a label that no node of a graph carries matches nothing
+ * there.  n == 0 or n_sets == 0 gives zero words and NEMO_OK (the counts of
+ * n_sets sets over no list position are 0).
+ * NEMO_ERR_INVALID, all checked on the host before anything is uploaded: a
+ * decreasing set_off, a label equal to UINT32_MAX, flags other than 0 or
+ * NEMO_KL_SINKS, cond outside 0 / 1.  An iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; a node context returns NEMO_ERR_STATE.  n * n_chunks > 2^28
+ * words, more than 2^32 - 1 labels named in all, or more than 2^32 - 1 sets, is
+ * NEMO_ERR_LIMIT: tile the call (the limits are read from n, n_sets and set_off
+ * alone, before any label is).
+ * The call blocks until the words and counts are on the host, as the knock-out
+ * calls do.  The results are the call's own state: valid until the next
+ * nemo_knockout_labels or nemo_load_corpus (the fetches return NEMO_ERR_STATE
+ * otherwise), independent of the knock-out, cut, diff, symmetric diff, nearest
+ * and class state in both directions.                                          */
+#define NEMO_KL_SINKS 1u  /* only sink goals (goals without children) match a label */
+int nemo_knockout_labels(nemo_ctx *ctx, const uint32_t *iters, size_t n, int cond,
+                         const uint64_t *set_off, const uint32_t *set_labels, size_t n_sets,
+                         uint32_t flags);
+/* n * n_chunks words each, n_chunks = ceil(n_sets / 64); word [i * n_chunks + c], bit s & 63;
+ * either pointer may be NULL; cap_words >= n * n_chunks                        */
+int nemo_fetch_knockout_labels(nemo_ctx *ctx, uint64_t *lost, uint64_t *hit, uint64_t cap_words);
+/* per set: list positions lost, list positions hit; cap >= n_sets each         */
+int nemo_fetch_knockout_label_counts(nemo_ctx *ctx, uint32_t *n_lost, uint32_t *n_hit, uint64_t cap);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

@@ -335,6 +335,14 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.cut_grid = value < 0 ? 0u : (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF);
     return NEMO_OK;
   }
+  if (!strcmp(name, "kl_grid")) {  // most workgroups of the label knock-out's sweeps; 0 / -1: as many as are resident
+    c->opt.kl_grid = value < 0 ? 0u : (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF);
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "kl_hitlist")) {  // 0: k_kl_lds without the hit list (V probes per chunk); 1 / -1: with it
+    c->opt.kl_hitlist = value != 0;
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;

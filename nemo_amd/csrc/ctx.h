@@ -20,6 +20,7 @@
 #include "device.h"
 #include "gdedup_host.h"
 #include "internal.h"
+#include "klabel_host.h"
 #include "knock_host.h"
 #include "nearest_host.h"
 #include "node.h"
@@ -155,6 +156,8 @@ struct Options {
   uint32_t near_ksplit = 0;                   // k_near_isect's K ranges (0: by the tile count and the device)
   uint32_t knock_lds_max = KO_LDS_MAX;        // largest LDS image (bytes) k_ko_lds takes (0: every graph to k_ko_glob)
   uint32_t cut_grid = 0;                      // test knob: most workgroups of k_cut_lds / k_cut_glob (0: as many as are resident)
+  bool kl_hitlist = true;                     // option kl_hitlist 0: k_kl_lds probes every node's label per chunk (the measured alternative)
+  uint32_t kl_grid = 0;                       // test knob: most workgroups of k_kl_lds / k_kl_glob (0: as many as are resident)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -332,6 +335,24 @@ struct CorpusState : GraphSizes {
   DevBuf<uint32_t> d_cutscan;        // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
   DevBuf<uint32_t> d_cutrows;        // [rows][4] nemo_cut
 
+  // knock-out by label (k_klabel.hip): the call's own state, void after the next nemo_knockout_labels or load;
+  // independent of knock-out, cut, diff, nearest and class state.  The eight buffers grow as one group, only
+  // inside nemo_knockout_labels, each to the largest request so far, behind a wait for the stream, in this order
+  bool kl_done = false;
+  uint64_t kl_n = 0, kl_sets = 0, kl_chunks = 0;  // list positions, sets and chunks of the last call
+  std::vector<uint32_t> kl_nlev;     // [G] the graphs' Kahn level counts (the tier), read once per load
+  std::vector<uint64_t> kl_setoff;   // the last call's uploads: set offsets from the first set's,
+  std::vector<uint64_t> kl_taboff;   // ... the tables' first slots,
+  std::vector<uint32_t> kl_desc;     // ... [n] graphs | the LDS tier's list positions | the global tier's
+  DevBuf<uint64_t> d_klset;          // [sets + 1]
+  DevBuf<uint32_t> d_kllab;          // the sets' labels
+  DevBuf<uint64_t> d_kltoff;         // [chunks + 2]
+  DevBuf<uint32_t> d_klkey;          // the tables' keys: per chunk, then the union filter
+  DevBuf<uint64_t> d_klmask;         // ... and masks
+  DevBuf<uint32_t> d_kldesc;         // [2 n]
+  DevBuf<uint64_t> d_klout;          // [n][chunks][2] (lost, hit), then the counts (u32: [chunks * 64] lost | hit)
+  DevBuf<uint64_t> d_klreg;          // the workgroups' regions: hit-list spill, k_kl_glob's dead words
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -416,11 +437,12 @@ struct nemo_ctx {
   hipEvent_t ev_whole = nullptr;   // ensure_whole's replicate is queued on `stream`: `aux` waits for it
   hipEvent_t ev_knock = nullptr;   // the knock-out calls' counts / rows have reached pinned memory
   hipEvent_t ev_cuts = nullptr;    // nemo_min_cuts' counts / words / totals / rows have reached pinned memory
-  hipEvent_t *const events[23] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_klabel = nullptr;  // nemo_knockout_labels' level counts / words / counts have reached pinned memory
+  hipEvent_t *const events[24] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
-                                  &ev_cuts};
+                                  &ev_cuts,    &ev_klabel};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -434,12 +456,13 @@ struct nemo_ctx {
   Pinned<uint32_t> h_near;  // nemo_nearest_runs: [n_q][4] rows, then the label maximum
   Pinned<uint32_t> h_knock;  // the knock-out calls: the listed graphs' (leaves, Kahn levels), then the rows
   Pinned<uint32_t> h_cuts;   // nemo_min_cuts: counts, round 1's words and the candidates, the totals, then the rows
-  void **const pinned[24] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint64_t> h_klabel;  // nemo_knockout_labels: the level counts; then the (lost, hit) words and the counts
+  void **const pinned[25] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
-                             h_cuts.slot()};
+                             h_cuts.slot(),  h_klabel.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

@@ -205,6 +205,37 @@ void launch_cut_glob(const DevCorpus &c, const CutArgs &a, uint32_t grid, hipStr
 void launch_cut_count(const CutArgs &a, hipStream_t s);  // a.scan[k] = popcount(a.words[k]), a.scan[n_chunks] = 0
 void launch_cut_emit(const CutArgs &a, hipStream_t s);   // the rows of the round's set bits at a.rows, by a.scan
 
+// One nemo_knockout_labels call (k_klabel.hip): hypotheses are label sets in chunks of 64, shared by every listed
+// graph; table c (c < n_chunks) maps a label to the mask of chunk c's sets that name it, table n_chunks is the
+// union filter of all named labels (klabel_host.h: key = label + 1, 0 empty, linear probing).
+struct KlArgs {
+  const uint64_t *set_off;   // [n_sets + 1] offsets into labels (k_kl_tables)
+  const uint32_t *labels;    // the sets' labels
+  uint32_t n_sets, n_chunks;
+  const uint64_t *tab_off;   // [n_chunks + 2] first slot of every table
+  uint32_t *key;             // [tab_off[n_chunks + 1]] the tables' keys
+  uint64_t *mask;            // ... and masks (the union filter's stay unused)
+  const uint32_t *graph;     // [n] list position -> graph
+  const uint32_t *pos;       // [n_tier] the launched tier's list positions
+  uint32_t n_tier;           // list positions of the launched tier
+  uint32_t parts;            // chunk ranges per graph (klabel::split)
+  uint32_t sinks;            // 1: only sink goals match (NEMO_KL_SINKS)
+  uint32_t no_list;          // 1: k_kl_lds without the hit list, V probes per chunk (option kl_hitlist 0)
+  uint32_t lds_total;        // k_kl_lds: the launch's dynamic LDS; what the image leaves holds the hit list's head
+  uint64_t *region;          // [workgroups][region_words] hit-list spill (and k_kl_glob's dead words)
+  uint64_t region_words;     // u64 per workgroup
+  uint64_t dead_words;       // k_kl_glob: dead words at the region's start (the hit list follows)
+  uint64_t *out;             // [n][n_chunks][2] (lost, hit)
+  uint32_t n;                // list positions of the call (k_kl_count)
+  uint32_t *cnt;             // k_kl_count: [n_chunks * 64] n_lost | [n_chunks * 64] n_hit
+};
+void launch_kl_tables(const KlArgs &a, hipStream_t s);
+// the workgroups of k_kl_lds resident on the device at lds_bytes of dynamic LDS (0: the query failed)
+uint32_t kl_lds_resident(uint32_t lds_bytes, uint32_t n_cu, bool list = true);
+void launch_kl_lds(const DevCorpus &c, const KlArgs &a, uint32_t grid, hipStream_t s);  // a.lds_total bytes of LDS
+void launch_kl_glob(const DevCorpus &c, const KlArgs &a, uint32_t grid, hipStream_t s);
+void launch_kl_count(const KlArgs &a, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

@@ -44,6 +44,7 @@ KNOCK_DTYPE = np.dtype([("graph", np.uint32), ("node", np.uint32), ("n_dead", np
 KO_MASKS = 1  # NEMO_KO_MASKS
 # struct nemo_cut (nemo_fetch_min_cuts)
 CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (3,))])
+KL_SINKS = 1  # NEMO_KL_SINKS
 
 
 def header_symbols() -> List[str]:
@@ -122,6 +123,9 @@ def lib():
             "nemo_min_cuts": ([vp, u32, i32, vp, sz, u32, u32], i32),
             "nemo_fetch_min_cuts": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_min_cut_stats": ([vp, vp], i32),
+            "nemo_knockout_labels": ([vp, vp, sz, i32, vp, vp, sz, u32], i32),
+            "nemo_fetch_knockout_labels": ([vp, vp, vp, u64], i32),
+            "nemo_fetch_knockout_label_counts": ([vp, vp, vp, u64], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -416,6 +420,39 @@ class Engine:
         out = np.zeros(9, np.uint64)
         self._chk(self.L.nemo_fetch_min_cut_stats(self.h, _p(out)))
         return out.reshape(3, 3)
+
+    def knockout_labels(self, iters: Sequence[int], cond: int, sets, sinks_only: bool = False):
+        """nemo_knockout_labels: hypotheses that name interned labels, tested on every listed run's pre (cond 0) or
+        post (cond 1) graph in one call.  sets: a list of label lists, or a pair (set_off u64 [n_sets + 1],
+        set_labels u32).  A set removes every node of a graph whose label it names (sinks_only: every sink goal).
+        Returns (lost, hit), uint64 arrays of shape (n, n_chunks), n_chunks = ceil(n_sets / 64): bit s & 63 of
+        word [i, s // 64] is set s on list position i; knockout_label_counts() has the per-set counts."""
+        if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+            off = np.ascontiguousarray(sets[0], dtype=np.uint64)
+            labels = np.ascontiguousarray(sets[1], dtype=np.uint32)
+            n_sets = max(len(off) - 1, 0)
+        else:
+            n_sets = len(sets)
+            off = np.zeros(n_sets + 1, np.uint64)
+            off[1:] = np.cumsum([len(x) for x in sets], dtype=np.uint64)
+            labels = np.ascontiguousarray([v for x in sets for v in x], dtype=np.uint32)
+        it = np.ascontiguousarray(iters, dtype=np.uint32)
+        self._kl_shape = (0, 0, 0)
+        self._chk(self.L.nemo_knockout_labels(self.h, _p(it), len(it), int(cond), off.ctypes.data, _p(labels), n_sets,
+                                              KL_SINKS if sinks_only else 0))
+        n_chunks = (n_sets + 63) // 64
+        self._kl_shape = (len(it), n_chunks, n_sets)
+        lost, hit = np.zeros((len(it), n_chunks), np.uint64), np.zeros((len(it), n_chunks), np.uint64)
+        self._chk(self.L.nemo_fetch_knockout_labels(self.h, _p(lost), _p(hit), lost.size))
+        return lost, hit
+
+    def knockout_label_counts(self):
+        """nemo_fetch_knockout_label_counts: (n_lost, n_hit) of the last knockout_labels call, per set the list
+        positions on which it is lost / hits a node (a run listed twice counts twice)."""
+        n_sets = getattr(self, "_kl_shape", (0, 0, 0))[2]
+        n_lost, n_hit = np.zeros(n_sets, np.uint32), np.zeros(n_sets, np.uint32)
+        self._chk(self.L.nemo_fetch_knockout_label_counts(self.h, _p(n_lost), _p(n_hit), n_sets))
+        return n_lost, n_hit
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
         """nemo_goal_labels: [n, label...] of a run's goal labels into device memory."""
