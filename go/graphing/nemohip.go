@@ -935,6 +935,61 @@ func (n *Neo4J) KnockoutLabels(iters []uint, cond string, sets [][]uint32, sinks
 	return res, nil
 }
 
+// LabelCut is one minimal cut by label: a smallest set of events whose joint
+// loss defeats the outcome on at least the asked number of listed runs.
+type LabelCut struct {
+	Labels []uint32 // interned labels, in candidate-list order
+	NLost  uint32   // the listed runs it breaks (a run listed twice counts twice)
+}
+
+// MinLabelCuts searches where KnockoutLabels evaluates (nemo_min_label_cuts):
+// among the candidate labels it returns every minimal set of at most maxSize
+// (1..3) events whose loss defeats the outcome on at least minRuns of the
+// listed runs' pre or post provenance (0: on every one of them).  It is the
+// question of lineage-driven fault injection across runs; the reference's
+// graphing package has no counterpart.  The cuts come sorted by size, then by
+// the colex rank of their positions in the list of live candidates.  The
+// second result holds, per size 1..3, the live candidates entering the round,
+// the hypotheses evaluated and the minimal cuts found.
+func (n *Neo4J) MinLabelCuts(iters []uint, cond string, candLabels []uint32, maxSize uint, minRuns uint, sinksOnly bool) ([]*LabelCut, [9]uint64, error) {
+	var stats [9]uint64
+	its := make([]C.uint32_t, len(iters)+1)
+	for i, it := range iters {
+		its[i] = C.uint32_t(it)
+	}
+	cand := make([]C.uint32_t, len(candLabels)+1) // never empty: &cand[0] below
+	for i, l := range candLabels {
+		cand[i] = C.uint32_t(l)
+	}
+	var flags C.uint32_t
+	if sinksOnly {
+		flags = C.NEMO_KL_SINKS
+	}
+	if err := n.err(C.nemo_min_label_cuts(n.ctx, &its[0], C.size_t(len(iters)), condIndex(cond), &cand[0], C.size_t(len(candLabels)), C.uint32_t(maxSize), C.uint32_t(minRuns), flags)); err != nil {
+		return nil, stats, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_min_label_cuts(n.ctx, nil, nil, 0, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	rows, nLost := make([]C.nemo_label_cut, cnt+1), make([]C.uint32_t, cnt+1)
+	if err := n.err(C.nemo_fetch_min_label_cuts(n.ctx, &rows[0], &nLost[0], cnt, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	if err := n.err(C.nemo_fetch_min_label_cut_stats(n.ctx, (*C.uint64_t)(unsafe.Pointer(&stats[0])))); err != nil {
+		return nil, stats, err
+	}
+	res := make([]*LabelCut, cnt)
+	for k, lc := range rows[:cnt] {
+		m := &LabelCut{NLost: uint32(nLost[k])}
+		for j := 0; j < int(lc.size); j++ {
+			m.Labels = append(m.Labels, uint32(lc.label[j]))
+		}
+		res[k] = m
+	}
+	return res, stats, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

@@ -244,8 +244,9 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *   "knock_lds_max"     largest LDS image (bytes) of a graph the knock-out sweep runs
  *                       in LDS; graphs past it, and graphs of 65536 nodes or more, run
  *                       the sweep over the CSR in device memory (default and upper
- *                       bound 81920; 0 = every graph in device memory); nemo_min_cuts
- *                       takes its tier from the same option
+ *                       bound 81920; 0 = every graph in device memory); nemo_min_cuts,
+ *                       nemo_knockout_labels and nemo_min_label_cuts take their tier
+ *                       from the same option
  *   "cut_grid"          most workgroups of nemo_min_cuts' persistent sweeps (0, default:
  *                       as many as are resident on the device, at most one per chunk
  *                       of 64 hypotheses); a test knob: 1 makes one workgroup take
@@ -254,7 +255,8 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       default: as many as are resident on the device); the twin of
  *                       "cut_grid", a test knob: 1 makes one workgroup walk every
  *                       listed graph in turn, small values split a graph's chunks
- *                       into few ranges; the tier is "knock_lds_max"'s
+ *                       into few ranges; the tier is "knock_lds_max"'s;
+ *                       nemo_min_label_cuts' sweeps take the same cap
  *   "kl_hitlist"        1 (default, also -1): the LDS-tier sweep of nemo_knockout_labels
  *                       lists, once per graph, the nodes whose label some set names,
  *                       and a chunk of 64 sets probes its table with those alone.  0:
@@ -642,6 +644,66 @@ int nemo_knockout_labels(nemo_ctx *ctx, const uint32_t *iters, size_t n, int con
 int nemo_fetch_knockout_labels(nemo_ctx *ctx, uint64_t *lost, uint64_t *hit, uint64_t cap_words);
 /* per set: list positions lost, list positions hit; cap >= n_sets each         */
 int nemo_fetch_knockout_label_counts(nemo_ctx *ctx, uint32_t *n_lost, uint32_t *n_hit, uint64_t cap);
+
+/* ---- minimal cut sets by label: the smallest fault sets that defeat every listed run ----
+ * The search over events across runs: which one, two or three events, lost
+ * together, defeat the outcome on all of the listed runs, or on at least q of
+ * them.  The subject (a raw loaded graph), dead_F(v), the roots and "the outcome
+ * is lost under F" (roots_dead == n_roots > 0) are the knock-out definitions
+ * above; F(i,S) is nemo_knockout_labels' definition: every node of graph
+ * g = 2 * run_index(iters[i]) + cond, goal or rule, whose label is in S.  Under
+ * NEMO_KL_SINKS only sink goals are in F(i,S).  flags is 0 or NEMO_KL_SINKS.
+ * Cuts: lost_count(S) is the number of list positions i on which the outcome is
+ * lost under F(i,S); a run listed twice counts twice.  q = min_runs, where 0
+ * means n; min_runs > n is NEMO_ERR_INVALID.  S is a cut iff n > 0 and
+ * lost_count(S) >= q.  lost is monotone in S, so lost_count is, every superset
+ * of a cut is a cut, and a cut is minimal iff no proper subset of it is a cut.
+ * The call returns all minimal cuts of size <= max_size among the candidates;
+ * max_size must be 1, 2 or 3 (NEMO_ERR_INVALID otherwise).  A listed graph
+ * without roots is never lost: under q = n such a list yields zero rows.
+ * Candidates: cand_labels[0 .. n_cand) must be distinct and differ from
+ * UINT32_MAX, which is no label.  A duplicate, or a label equal to UINT32_MAX,
+ * is NEMO_ERR_INVALID, checked on the host before anything is uploaded; the
+ * message gives the position of the offence and the label.  cand_labels == NULL
+ * with n_cand > 0 is NEMO_ERR_INVALID: there is no implicit list.
+ * Rounds: round 1 evaluates the K singletons on every list position and keeps
+ * the lost bit and the hit bit.  The live list holds, in candidate order, the
+ * candidates that are no cut alone and that hit at least one listed graph, K1
+ * entries (a label that hits no listed node can be in no minimal cut: S and S
+ * without it remove the same nodes).  Round 2 evaluates all C(K1,2) pairs of
+ * live positions; every pair with lost_count >= q is minimal.  Round 3
+ * evaluates all C(K1,3) triples; a triple with lost_count >= q is minimal iff
+ * none of its three pairs was a cut in round 2.
+ * Hypothesis index: the colex rank of nemo_min_cuts over the live positions
+ * (a < b < c: C(c,3) + C(b,2) + a, pairs C(b,2) + a, singles a).  The rows are
+ * sorted by (size, rank); a row's labels are in candidate-list order, unused
+ * entries UINT32_MAX; n_lost[k] is lost_count of row k.
+ * n == 0 or n_cand == 0 gives zero rows and NEMO_OK.  A round of more than
+ * 2^32 - 2 hypotheses, or a round with n * ceil(hyps / 64) > 2^28 words, is
+ * NEMO_ERR_LIMIT (shorten the candidate list or the run list); both limits are
+ * checked per round, before that round's launch (K1 is known only after round
+ * 1), and the call then leaves no results.  An iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; cond outside 0 / 1 and unknown flags are NEMO_ERR_INVALID;
+ * a node context, and a call without a loaded corpus, return NEMO_ERR_STATE.
+ * The call blocks until the rows are on the host.  The results are the call's
+ * own state: valid until the next nemo_min_label_cuts or nemo_load_corpus (the
+ * fetches return NEMO_ERR_STATE otherwise), independent of the knock-out, cut,
+ * label knock-out, diff, symmetric diff, nearest and class state in both
+ * directions.  No option of its own: the tier is "knock_lds_max"'s, the grid cap
+ * "kl_grid"'s.                                                                 */
+typedef struct nemo_label_cut {
+  uint32_t size;     /* 1..3                                                         */
+  uint32_t label[3]; /* labels in candidate-list order, unused = UINT32_MAX          */
+} nemo_label_cut;
+int nemo_min_label_cuts(nemo_ctx *ctx, const uint32_t *iters, size_t n, int cond,
+                        const uint32_t *cand_labels, size_t n_cand, uint32_t max_size,
+                        uint32_t min_runs, uint32_t flags);
+/* out[k] for every minimal cut k, n_lost[k] its lost_count (n_lost may be NULL);
+ * out == NULL queries *n_out.                                                  */
+int nemo_fetch_min_label_cuts(nemo_ctx *ctx, nemo_label_cut *out, uint32_t *n_lost, uint64_t cap, uint64_t *n_out);
+/* As nemo_fetch_min_cut_stats: per size s = 1..3, out[3 (s - 1) ..]: live
+ * candidates entering the round, hypotheses evaluated, minimal cuts found.     */
+int nemo_fetch_min_label_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

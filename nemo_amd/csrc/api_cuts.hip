@@ -3,47 +3,6 @@
 
 namespace {
 
-struct CutTimer {  // the outer group: every launch of the call between one pair of events
-  nemo_ctx *c;
-  hipEvent_t ta = nullptr;
-  explicit CutTimer(nemo_ctx *c_) : c(c_) {
-    const bool on = c->timing && (c->tgroups.empty() || std::find(c->tgroups.begin(), c->tgroups.end(), "k_cuts") != c->tgroups.end());
-    if (on) {
-      ta = get_event(c);
-      hipEventRecord(ta, c->stream);
-    }
-  }
-  void done(double bytes, double ops) {
-    if (!ta) return;
-    hipEvent_t tb = get_event(c);
-    hipEventRecord(tb, c->stream);
-    c->pending.push_back({"k_cuts", ta, tb, bytes, ops});
-    ta = nullptr;
-  }
-  ~CutTimer() {
-    if (ta) c->ev_pool.push_back(ta);
-  }
-};
-
-// `need` elements in each buffer of a group that grows together: each to the largest request so far, released
-// together and allocated in the given order, behind a wait for the stream (an earlier launch may still read them)
-template <class... B>
-int cut_grow(nemo_ctx *c, const uint64_t *need, B &...bufs) {
-  bool ok = true;
-  int i = 0;
-  ((ok = ok && bufs.p && need[i++] <= bufs.cap), ...);
-  if (ok) return NEMO_OK;
-  uint64_t cap[sizeof...(B)];
-  i = 0;
-  ((cap[i] = std::max<uint64_t>(need[i], bufs.cap), i++), ...);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  (bufs.release(c), ...);
-  int rc = NEMO_OK;
-  i = 0;
-  ((rc = rc ? rc : bufs.grow(c, cap[i++])), ...);
-  return rc;
-}
-
 int cut_wait(nemo_ctx *c) {  // the copies queued so far have reached pinned memory
   HIPCHK(c, hipEventRecord(c->ev_cuts, c->stream));
   HIPCHK(c, hipEventSynchronize(c->ev_cuts));
@@ -97,7 +56,7 @@ int nemo_min_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t *can
   if ((rc = ensure_event(c, &c->ev_cuts))) return rc;
   if ((rc = c->h_cuts.grow(c, 8))) return rc;
   hipStream_t s = c->stream;
-  CutTimer timer(c);
+  GroupTimer timer(c, "k_cuts");
   if (!cs.d_cutdesc.p) {
     HIPCHK(c, hipStreamSynchronize(s));
     if ((rc = cs.d_cutdesc.grow(c, 8))) return rc;
@@ -151,7 +110,7 @@ int nemo_min_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t *can
   const uint64_t ck1 = cuts::chunks(K);
   {
     const uint64_t need[4] = {K, 2 * K, ck1, lds ? 1 : dw * cuts::grid(cuts::chunks(most), resident, c->opt.cut_grid)};
-    if ((rc = cut_grow(c, need, cs.d_cutcand, cs.d_cutlive, cs.d_cutw[0], cs.d_cutdead))) return rc;
+    if ((rc = grow_group(c, need, cs.d_cutcand, cs.d_cutlive, cs.d_cutw[0], cs.d_cutdead))) return rc;
   }
   if ((rc = c->h_cuts.grow(c, 2 * ck1 + K + 8))) return rc;
   if (cand) {
@@ -208,7 +167,7 @@ int nemo_min_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t *can
   const uint64_t n_scan = ck[0] + ck[1] + ck[2] + 3;
   {
     const uint64_t need[3] = {ck[1], ck[2], n_scan + nemo::dx_scan_tiles((uint32_t)(std::max(ck[0], std::max(ck[1], ck[2])) + 1))};
-    if ((rc = cut_grow(c, need, cs.d_cutw[1], cs.d_cutw[2], cs.d_cutscan))) return rc;
+    if ((rc = grow_group(c, need, cs.d_cutw[1], cs.d_cutw[2], cs.d_cutscan))) return rc;
   }
   if (max_size >= 2 && K1) {
     cs.cut_live.resize(2 * K1);

@@ -3,47 +3,6 @@
 
 namespace {
 
-struct KlTimer {  // the outer group: every launch of the call between one pair of events
-  nemo_ctx *c;
-  hipEvent_t ta = nullptr;
-  explicit KlTimer(nemo_ctx *c_) : c(c_) {
-    const bool on = c->timing && (c->tgroups.empty() || std::find(c->tgroups.begin(), c->tgroups.end(), "k_klabel") != c->tgroups.end());
-    if (on) {
-      ta = get_event(c);
-      hipEventRecord(ta, c->stream);
-    }
-  }
-  void done(double bytes, double ops) {
-    if (!ta) return;
-    hipEvent_t tb = get_event(c);
-    hipEventRecord(tb, c->stream);
-    c->pending.push_back({"k_klabel", ta, tb, bytes, ops});
-    ta = nullptr;
-  }
-  ~KlTimer() {
-    if (ta) c->ev_pool.push_back(ta);
-  }
-};
-
-// `need` elements in each buffer of the group: each to the largest request so far, released together and
-// allocated in the given order, behind a wait for the stream (an earlier launch may still read them)
-template <class... B>
-int kl_grow(nemo_ctx *c, const uint64_t *need, B &...bufs) {
-  bool ok = true;
-  int i = 0;
-  ((ok = ok && bufs.p && need[i++] <= bufs.cap), ...);
-  if (ok) return NEMO_OK;
-  uint64_t cap[sizeof...(B)];
-  i = 0;
-  ((cap[i] = std::max<uint64_t>(need[i], bufs.cap), i++), ...);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  (bufs.release(c), ...);
-  int rc = NEMO_OK;
-  i = 0;
-  ((rc = rc ? rc : bufs.grow(c, cap[i++])), ...);
-  return rc;
-}
-
 int kl_wait(nemo_ctx *c) {  // the copies queued so far have reached pinned memory
   HIPCHK(c, hipEventRecord(c->ev_klabel, c->stream));
   HIPCHK(c, hipEventSynchronize(c->ev_klabel));
@@ -140,7 +99,7 @@ int nemo_knockout_labels(nemo_ctx *c, const uint32_t *iters, size_t n, int cond,
     const uint32_t *lv = reinterpret_cast<const uint32_t *>(c->h_klabel.p);
     cs.kl_nlev.assign(lv, lv + cs.G);
   }
-  KlTimer timer(c);
+  GroupTimer timer(c, "k_klabel");
   // the tiers, the launch's LDS and what a workgroup keeps in device memory
   uint32_t n_lds = 0, n_glob = 0, image = 0;
   uint64_t glob_v = 0;
@@ -188,7 +147,7 @@ int nemo_knockout_labels(nemo_ctx *c, const uint32_t *iters, size_t n, int cond,
   {
     const uint64_t need[8] = {n_sets + 1, std::max<uint64_t>(n_labels, 1), ck + 2, slots, mslots, 2 * (uint64_t)n, out_words,
                               std::max<uint64_t>(1, std::max<uint64_t>(n_lds ? grid_lds * rw_lds : 0ull, n_glob ? grid_glob * rw_glob : 0ull))};
-    if ((rc = kl_grow(c, need, cs.d_klset, cs.d_kllab, cs.d_kltoff, cs.d_klkey, cs.d_klmask, cs.d_kldesc, cs.d_klout, cs.d_klreg)))
+    if ((rc = grow_group(c, need, cs.d_klset, cs.d_kllab, cs.d_kltoff, cs.d_klkey, cs.d_klmask, cs.d_kldesc, cs.d_klout, cs.d_klreg)))
       return rc;
   }
   if ((rc = c->h_klabel.grow(c, out_words))) return rc;

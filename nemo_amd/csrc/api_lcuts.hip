@@ -1,0 +1,333 @@
+// api_lcuts.hip — nemo_min_label_cuts and its fetches (k_lcuts.hip, lcut_host.h; DESIGN.md §Minimal cut sets by label).
+#include "ctx.h"
+
+namespace {
+
+int lc_wait(nemo_ctx *c) {  // the copies queued so far have reached pinned memory
+  HIPCHK(c, hipEventRecord(c->ev_lcuts, c->stream));
+  HIPCHK(c, hipEventSynchronize(c->ev_lcuts));
+  return NEMO_OK;
+}
+
+// What a workgroup of k_lc_lds takes of a CU's LDS beside its dynamic part: the kernel's static LDS (48 bytes by the
+// compiler's report), rounded up to whole allocation granules with one to spare.  A value too small cannot cost a
+// resident workgroup: the second occupancy query below refuses the larger size then.
+#define LC_LDS_STATIC 512
+
+// Round `size`'s dynamic LDS: the largest image plus the `list` bytes of the longest hit list behind it, as far as
+// a workgroup may take them while as many workgroups stay resident per CU; what does not fit goes to the workgroup's
+// region.  *resident: those workgroups on the whole device.  (The residency query raises the kernel's
+// MaxDynamicSharedMemorySize, a permission, not an allocation; launch_lc_lds sets it to the launch's size.)
+int lc_lds_total(nemo_ctx *c, uint32_t size, uint32_t image, uint64_t list, uint32_t *total, uint32_t *resident) {
+  const uint32_t n_cu = c->cs.dc.n_cu;
+  const uint32_t base = nemo::lc_lds_resident(size, image, n_cu);
+  if (!base) return fail(c, NEMO_ERR_HIP, "nemo_min_label_cuts: no workgroup of k_lc_lds is resident at %u bytes of LDS", image);
+  *total = image, *resident = base;
+  int per_cu_lds = 0;
+  if (hipDeviceGetAttribute(&per_cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, c->device) != hipSuccess) {
+    (void)hipGetLastError();
+    return NEMO_OK;
+  }
+  const int64_t room = (int64_t)per_cu_lds / (base / n_cu) - LC_LDS_STATIC;
+  if (room <= (int64_t)image) return NEMO_OK;
+  const uint32_t more = (uint32_t)std::min<uint64_t>((uint64_t)room & ~15ull, image + ((list + 15) & ~15ull));
+  if (more > image && nemo::lc_lds_resident(size, more, n_cu) == base) *total = more;
+  return NEMO_OK;
+}
+
+struct LcPlan {  // one round's launches
+  uint32_t lds_total = 0;
+  uint64_t rw_lds = 0, rw_glob = 0;  // region words of a workgroup
+  uint64_t r_lds = 1, r_glob = 1;    // most workgroups
+};
+
+}  // namespace
+
+extern "C" {
+
+// The candidates are checked on the host and hashed into one table; the listed graphs go to the two tiers'
+// persistent sweeps by their LDS image, as in nemo_knockout_labels.  Round 1's cut and any-hit words come back to
+// the host (K / 4 bytes), which makes the live list and uploads it with its inverse; rounds 2 and 3 follow without
+// a round trip; the rounds' popcounts are scanned, the totals read in one blocking round trip, the rows and their
+// n_lost written and copied.
+int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, const uint32_t *cand_labels, size_t n_cand,
+                        uint32_t max_size, uint32_t min_runs, uint32_t flags) {
+  if (c && c->node)
+    return fail(c, NEMO_ERR_STATE, "nemo_min_label_cuts: single-device contexts only (a node context does not fan it out)");
+  if (!c) return NEMO_ERR_INVALID;
+  CorpusState &cs = c->cs;
+  if (!cs.loaded) return fail(c, NEMO_ERR_STATE, "nemo_min_label_cuts without a loaded corpus (the last load failed?)");
+  cs.lc_done = false;  // from here on a failed call leaves no results
+  if (!iters && n) return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: no run list for %zu list positions", n);
+  if (cond != 0 && cond != 1) return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: cond must be 0 (pre) or 1 (post)");
+  if (flags & ~NEMO_KL_SINKS) return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: unknown flags %#x", flags);
+  if (max_size < 1 || max_size > CUT_MAX_SIZE)
+    return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: max_size must be 1, 2 or 3 (%u)", max_size);
+  uint32_t q = 0;
+  if (!lcuts::min_runs(n, min_runs, &q))
+    return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: min_runs %u exceeds the %zu list positions", min_runs, n);
+  if (!cand_labels && n_cand)
+    return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: no candidate list (there is no implicit one)");
+  const uint64_t K = n_cand;
+  {
+    size_t where = 0;
+    switch (lcuts::check_cands(cand_labels, n_cand, &where)) {
+      case cuts::CAND_RANGE:
+        return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: candidate %zu is label %u (UINT32_MAX), which is no label", where,
+                    cand_labels[where]);
+      case cuts::CAND_DUP:
+        return fail(c, NEMO_ERR_INVALID, "nemo_min_label_cuts: candidate %zu names label %u a second time", where, cand_labels[where]);
+      default:
+        break;
+    }
+  }
+  std::vector<uint32_t> &desc = cs.lc_desc;  // [n] graphs | the tiers' list positions
+  desc.assign(2 * n, 0u);
+  int rc;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t r;
+    if ((rc = run_index(c, iters[i], &r))) return rc;
+    desc[i] = 2 * r + (uint32_t)cond;
+  }
+  auto limit = [&](uint64_t k, uint32_t sz) -> int {
+    switch (lcuts::round_check(n, k, sz)) {
+      case lcuts::ROUND_HYPS:
+        return fail(c, NEMO_ERR_LIMIT,
+                    "nemo_min_label_cuts: the sets of %u of %llu live candidates exceed 2^32 - 2 hypotheses: shorten the candidate list or the run list",
+                    sz, (unsigned long long)k);
+      case lcuts::ROUND_WORDS:
+        return fail(c, NEMO_ERR_LIMIT,
+                    "nemo_min_label_cuts: %zu list positions x %llu chunks of 64 sets of %u exceed 2^28 words: shorten the candidate list or the run list",
+                    n, (unsigned long long)cuts::chunks(cuts::round_hyps(k, sz)), sz);
+      default:
+        return NEMO_OK;
+    }
+  };
+  if (n && K && (rc = limit(K, 1))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_whole(c))) return rc;  // may read any graph's build outputs
+  if ((rc = ensure_load_checked(c))) return rc;
+  std::fill(cs.lc_stats, cs.lc_stats + 9, 0ull);
+  cs.lc_rows = 0;
+  if (!n || !K) {  // zero hypotheses, or no list position to lose them on
+    cs.lc_done = true;
+    return NEMO_OK;
+  }
+  if ((rc = ensure_event(c, &c->ev_lcuts))) return rc;
+  hipStream_t s = c->stream;
+  if (cs.kl_nlev.empty()) {  // once per load: a function of the loaded graphs (shared with nemo_knockout_labels)
+    if ((rc = c->h_lcuts.grow(c, cs.G + 8))) return rc;
+    nemo::launch_to_host(c->h_lcuts.p, cs.dc.nlev, 4ull * cs.G, s);
+    if ((rc = lc_wait(c))) return rc;
+    cs.kl_nlev.assign(c->h_lcuts.p, c->h_lcuts.p + cs.G);
+  }
+  GroupTimer timer(c, "k_lcuts");
+  // the tiers, the rounds' LDS and what a workgroup keeps in device memory
+  auto fits = [&](uint32_t g) { return knock::lds_fits(cs.nv(g), cs.ne(g), cs.kl_nlev[g], c->opt.knock_lds_max); };
+  auto image_of = [&](uint32_t g) { return knock::knock_lds_bytes((uint32_t)cs.nv(g), (uint32_t)cs.ne(g), cs.kl_nlev[g]); };
+  uint32_t n_lds = 0, n_glob = 0, image = 0;
+  uint64_t glob_v = 0, lds_v = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (fits(desc[i])) n_lds++, image = std::max(image, image_of(desc[i])), lds_v = std::max(lds_v, cs.nv(desc[i]));
+    else n_glob++, glob_v = std::max(glob_v, cs.nv(desc[i]));
+  }
+  {
+    uint32_t l = 0, gl = 0;
+    for (size_t i = 0; i < n; i++) {
+      if (fits(desc[i])) desc[n + l++] = (uint32_t)i;
+      else desc[n + n_lds + gl++] = (uint32_t)i;
+    }
+  }
+  const uint32_t cap = c->opt.kl_grid;
+  LcPlan plan[3];
+  uint64_t reg_need = 1;
+  for (uint32_t sz = 1; sz <= max_size; sz++) {  // K bounds every round's live positions
+    LcPlan &p = plan[sz - 1];
+    uint32_t res_lds = 1;
+    if (n_lds) {
+      if ((rc = lc_lds_total(c, sz, image, 4 * lcuts::list_entries(K, lds_v), &p.lds_total, &res_lds))) return rc;
+      for (size_t k = 0; k < n_lds; k++) {
+        const uint32_t g = desc[desc[n + k]];
+        p.rw_lds = std::max(p.rw_lds, lcuts::region_words(0, lcuts::list_entries(K, cs.nv(g)), (p.lds_total - image_of(g)) / 4u));
+      }
+    }
+    p.rw_glob = lcuts::region_words(knock::dead_words(glob_v), lcuts::list_entries(K, glob_v), 0);
+    p.r_lds = klabel::region_grid(res_lds, p.rw_lds), p.r_glob = klabel::region_grid(2ull * cs.dc.n_cu, p.rw_glob);
+    if (cap) p.r_lds = std::min<uint64_t>(p.r_lds, cap), p.r_glob = std::min<uint64_t>(p.r_glob, cap);
+    if (n_lds) reg_need = std::max(reg_need, p.r_lds * p.rw_lds);
+    if (n_glob) reg_need = std::max(reg_need, p.r_glob * p.rw_glob);
+  }
+  const uint64_t ck1 = cuts::chunks(K), slots = lcuts::table_slots(K);
+  {
+    const uint64_t need[10] = {K, 2 * K, K, slots, slots, 2 * (uint64_t)n, (uint64_t)n * ck1, reg_need, 2 * ck1, (uint64_t)n * ck1};
+    if ((rc = grow_group(c, need, cs.d_lccand, cs.d_lcmap, cs.d_lclive, cs.d_lckey, cs.d_lcval, cs.d_lcdesc, cs.d_lchit, cs.d_lcreg,
+                      cs.d_lcw[0], cs.d_lclost[0])))
+      return rc;
+  }
+  if ((rc = c->h_lcuts.grow(c, 4 * ck1 + 8))) return rc;
+  cs.lc_map.assign(2 * K, LC_NONE);
+  for (uint64_t p = 0; p < K; p++) cs.lc_map[p] = (uint32_t)p;  // round 1: every candidate is live
+  // (the call ends behind a wait for the stream: the caller's array outlives the copy)
+  HIPCHK(c, hipMemcpyAsync(cs.d_lccand.p, cand_labels, K * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(cs.d_lcmap.p, cs.lc_map.data(), K * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(cs.d_lcdesc.p, desc.data(), 2 * n * 4, hipMemcpyHostToDevice, s));
+  nemo::launch_zero(cs.d_lckey.p, 4 * slots, s);
+  nemo::LcArgs a[3] = {};
+  for (uint32_t k = 0; k < 3; k++) {
+    a[k].cand = cs.d_lccand.p, a[k].n_cand = (uint32_t)K, a[k].key = cs.d_lckey.p, a[k].val = cs.d_lcval.p, a[k].slots = slots;
+    a[k].size = k + 1, a[k].graph = cs.d_lcdesc.p, a[k].sinks = (flags & NEMO_KL_SINKS) ? 1u : 0u;
+    a[k].region = cs.d_lcreg.p, a[k].n = (uint32_t)n, a[k].q = q, a[k].hit = cs.d_lchit.p;
+  }
+  double bytes = 0, ops = 0;
+  {
+    const double b = 16.0 * (double)K;  // a label read, a key and a position written, the probe
+    if ((rc = timed(c, "k_lc_table", b, 0, [&] { nemo::launch_lc_table(a[0], s); }))) return rc;
+    bytes += b + 4.0 * (double)slots;
+  }
+  // One round: the two tiers' sweeps, then the reduction.  The byte model: a work item reads its graph's image
+  // (4 E + 12 V + 4 L + 8) and its 4 V labels twice (count, scatter); a chunk writes 8 bytes (round 1: 16);
+  // ops = E child words per chunk, an upper bound (the host does not know which chunks hit nothing and skip the
+  // sweep); the global tier adds 16 V per chunk for its dead words in device memory.  The reduction reads every
+  // word once and writes one per chunk.
+  auto round = [&](nemo::LcArgs &r) -> int {
+    if (!r.n_chunks) return NEMO_OK;
+    const LcPlan &p = plan[r.size - 1];
+    const uint64_t ck = r.n_chunks;
+    const double per_word = r.size == 1 ? 16.0 : 8.0;
+    for (int tier = 0; tier < 2; tier++) {
+      const uint32_t nt = tier ? n_glob : n_lds;
+      if (!nt) continue;
+      const uint64_t res = tier ? p.r_glob : p.r_lds;
+      const klabel::Split sp = klabel::split(nt, ck, res);
+      const uint32_t grid = klabel::grid(sp.items, res, cap);
+      double b = 0, o = 0;
+      for (uint32_t k = 0; k < nt; k++) {
+        const uint32_t g = desc[desc[n + (tier ? n_lds : 0) + k]];
+        const double V = (double)cs.nv(g), E = (double)cs.ne(g), L = (double)cs.kl_nlev[g];
+        b += sp.parts * (4.0 * E + 12.0 * V + 4.0 * L + 8.0 + 8.0 * V) + (double)ck * (per_word + (tier ? 16.0 * V : 0.0));
+        o += (double)ck * E;
+      }
+      r.pos = cs.d_lcdesc.p + n + (tier ? n_lds : 0);
+      r.n_tier = nt, r.parts = sp.parts;
+      r.lds_total = tier ? 0u : p.lds_total;
+      r.region_words = tier ? p.rw_glob : p.rw_lds;
+      r.dead_words = tier ? knock::dead_words(glob_v) : 0;
+      if (tier) rc = timed(c, "k_lc_glob", b, o, [&] { nemo::launch_lc_glob(cs.dc, r, grid, s); });
+      else rc = timed(c, "k_lc_lds", b, o, [&] { nemo::launch_lc_lds(cs.dc, r, grid, s); });
+      if (rc) return rc;
+      bytes += b, ops += o;
+    }
+    const double b_red = per_word * (double)n * (double)ck + per_word * (double)ck;
+    bytes += b_red;
+    return timed(c, "k_lc_reduce", b_red, 0, [&] { nemo::launch_lc_reduce(r, s); });
+  };
+  // round 1: every candidate is live
+  a[0].lmap = cs.d_lcmap.p, a[0].k1 = (uint32_t)K, a[0].n_hyp = (uint32_t)K, a[0].n_chunks = (uint32_t)ck1;
+  a[0].lost = cs.d_lclost[0].p, a[0].words = cs.d_lcw[0].p;
+  if ((rc = round(a[0]))) return rc;
+  nemo::launch_to_host(c->h_lcuts.p, cs.d_lcw[0].p, 16 * ck1, s);
+  if ((rc = lc_wait(c))) return rc;
+  const uint64_t *w1 = reinterpret_cast<const uint64_t *>(c->h_lcuts.p);
+  cs.lc_live = lcuts::live_list(w1, w1 + ck1, K);
+  const uint64_t K1 = cs.lc_live.size();
+  uint64_t n_hyp[3] = {K, 0, 0};
+  for (uint32_t sz = 2; sz <= max_size; sz++) {  // per round, before the round's launch: K1 is known only now
+    if ((rc = limit(K1, sz))) return rc;
+    n_hyp[sz - 1] = cuts::round_hyps(K1, sz);
+  }
+  const uint64_t ck[3] = {ck1, cuts::chunks(n_hyp[1]), cuts::chunks(n_hyp[2])};
+  const uint64_t scan_off[3] = {0, ck[0] + 1, ck[0] + ck[1] + 2};
+  const uint64_t n_scan = ck[0] + ck[1] + ck[2] + 3;
+  {
+    const uint64_t need[5] = {ck[1], ck[2], (uint64_t)n * ck[1], (uint64_t)n * ck[2],
+                              n_scan + nemo::dx_scan_tiles((uint32_t)(std::max(ck[0], std::max(ck[1], ck[2])) + 1))};
+    if ((rc = grow_group(c, need, cs.d_lcw[1], cs.d_lcw[2], cs.d_lclost[1], cs.d_lclost[2], cs.d_lcscan))) return rc;
+  }
+  if (max_size >= 2 && K1) {
+    const std::vector<uint32_t> map = lcuts::live_map(cs.lc_live, K);
+    std::copy(map.begin(), map.end(), cs.lc_map.begin() + K);
+    HIPCHK(c, hipMemcpyAsync(cs.d_lcmap.p + K, cs.lc_map.data() + K, K * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(cs.d_lclive.p, cs.lc_live.data(), K1 * 4, hipMemcpyHostToDevice, s));
+  }
+  for (uint32_t k = 1; k < max_size; k++) {
+    a[k].lmap = cs.d_lcmap.p + K, a[k].k1 = (uint32_t)K1, a[k].n_hyp = (uint32_t)n_hyp[k], a[k].n_chunks = (uint32_t)ck[k];
+    a[k].lost = cs.d_lclost[k].p, a[k].words = cs.d_lcw[k].p, a[k].pairs = k == 2 ? cs.d_lcw[1].p : nullptr;
+    if ((rc = round(a[k]))) return rc;
+  }
+  // popcounts, their scans, the totals: k_cuts.hip's row kernels over the cut words
+  nemo::CutArgs e[3] = {};
+  uint32_t *tsum = cs.d_lcscan.p + n_scan;
+  nemo::HostCopies hc;
+  for (uint32_t k = 0; k < max_size; k++) {
+    if (!a[k].n_chunks) continue;
+    e[k].size = k + 1, e[k].n_hyp = a[k].n_hyp, e[k].n_chunks = a[k].n_chunks, e[k].words = a[k].words;
+    e[k].cand = cs.d_lccand.p, e[k].live = k ? cs.d_lclive.p : nullptr;
+    e[k].scan = cs.d_lcscan.p + scan_off[k];
+    const double b = 12.0 * e[k].n_chunks;
+    if ((rc = timed(c, "k_cut_count", b, 0, [&] { nemo::launch_cut_count(e[k], s); }))) return rc;
+    if ((rc = timed(c, "k_cut_scan", 16.0 * e[k].n_chunks, 0, [&] { nemo::launch_scan(e[k].scan, e[k].n_chunks + 1, tsum, s); })))
+      return rc;
+    bytes += b + 16.0 * e[k].n_chunks;
+    hc.add(c->h_lcuts.p + k, e[k].scan + e[k].n_chunks, 4);
+  }
+  c->h_lcuts.p[0] = c->h_lcuts.p[1] = c->h_lcuts.p[2] = 0;
+  nemo::launch_to_host_multi(hc, s);
+  if ((rc = lc_wait(c))) return rc;
+  const uint64_t found[3] = {c->h_lcuts.p[0], c->h_lcuts.p[1], c->h_lcuts.p[2]};
+  const uint64_t rows = found[0] + found[1] + found[2];
+  if (rows) {
+    if (5 * rows > cs.d_lcrows.cap || !cs.d_lcrows.p) {
+      HIPCHK(c, hipStreamSynchronize(s));
+      if ((rc = cs.d_lcrows.grow(c, 5 * rows))) return rc;
+    }
+    if ((rc = c->h_lcuts.grow(c, 5 * rows))) return rc;
+    uint64_t base = 0;
+    for (uint32_t k = 0; k < max_size; k++) {
+      if (!a[k].n_chunks || !found[k]) continue;
+      e[k].rows = cs.d_lcrows.p + 4 * base;
+      const double b = 12.0 * e[k].n_chunks + 16.0 * (double)found[k] + 8.0 * (k + 1) * (double)found[k];
+      if ((rc = timed(c, "k_cut_emit", b, 0, [&] { nemo::launch_cut_emit(e[k], s); }))) return rc;
+      a[k].scan = e[k].scan, a[k].n_rows = (uint32_t)found[k], a[k].n_lost = cs.d_lcrows.p + 4 * rows + base;
+      const double b_sup = (double)found[k] * (8.0 * (double)n + 16.0);
+      if ((rc = timed(c, "k_lc_support", b_sup, 0, [&] { nemo::launch_lc_support(a[k], s); }))) return rc;
+      bytes += b + b_sup;
+      base += found[k];
+    }
+  }
+  timer.done(bytes, ops);
+  if (rows) {
+    nemo::launch_to_host(c->h_lcuts.p, cs.d_lcrows.p, 20 * rows, s);
+    if ((rc = lc_wait(c))) return rc;
+  }
+  for (uint32_t k = 0; k < max_size; k++) {
+    cs.lc_stats[3 * k] = k ? K1 : K;
+    cs.lc_stats[3 * k + 1] = n_hyp[k];
+    cs.lc_stats[3 * k + 2] = found[k];
+  }
+  cs.lc_rows = rows;
+  cs.lc_done = true;
+  return NEMO_OK;
+}
+
+int nemo_fetch_min_label_cuts(nemo_ctx *c, nemo_label_cut *out, uint32_t *n_lost, uint64_t cap, uint64_t *n_out) {
+  if (!c) return NEMO_ERR_INVALID;
+  if (c->node || !c->cs.lc_done)
+    return fail(c, NEMO_ERR_STATE, "nemo_fetch_min_label_cuts before nemo_min_label_cuts (or after a later nemo_load_corpus)");
+  const uint64_t n = c->cs.lc_rows;  // no ensure_whole: reads the last call's host rows, no graph
+  if (n_out) *n_out = n;
+  if (!out) return NEMO_OK;
+  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (n) memcpy(out, c->h_lcuts.p, n * sizeof(nemo_label_cut));
+  if (n && n_lost) memcpy(n_lost, c->h_lcuts.p + 4 * n, n * sizeof(uint32_t));
+  return NEMO_OK;
+}
+
+int nemo_fetch_min_label_cut_stats(nemo_ctx *c, uint64_t out[9]) {
+  if (!c || !out) return NEMO_ERR_INVALID;
+  if (c->node || !c->cs.lc_done)
+    return fail(c, NEMO_ERR_STATE, "nemo_fetch_min_label_cut_stats before nemo_min_label_cuts (or after a later nemo_load_corpus)");
+  memcpy(out, c->cs.lc_stats, sizeof c->cs.lc_stats);
+  return NEMO_OK;
+}
+
+}  // extern "C"

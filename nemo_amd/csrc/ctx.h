@@ -21,6 +21,7 @@
 #include "gdedup_host.h"
 #include "internal.h"
 #include "klabel_host.h"
+#include "lcut_host.h"
 #include "knock_host.h"
 #include "nearest_host.h"
 #include "node.h"
@@ -353,6 +354,30 @@ struct CorpusState : GraphSizes {
   DevBuf<uint64_t> d_klout;          // [n][chunks][2] (lost, hit), then the counts (u32: [chunks * 64] lost | hit)
   DevBuf<uint64_t> d_klreg;          // the workgroups' regions: hit-list spill, k_kl_glob's dead words
 
+  // minimal cut sets by label (k_lcuts.hip): the call's own state, void after the next nemo_min_label_cuts or load;
+  // independent of knock-out, cut, label knock-out, diff, nearest and class state (kl_nlev above is the load's, not
+  // a result).  All of it grows only inside nemo_min_label_cuts, each buffer to the largest request so far, behind
+  // a wait for the stream: the first ten together once the call is checked, in this order; d_lcw[1..2],
+  // d_lclost[1..2] and d_lcscan together once round 1 has left the live list; d_lcrows alone once the totals are known
+  bool lc_done = false;
+  uint64_t lc_rows = 0;              // rows of the last call (in nemo_ctx::h_lcuts: [rows][4], then [rows] n_lost)
+  uint64_t lc_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size: live candidates, hypotheses, minimal cuts
+  std::vector<uint32_t> lc_desc;     // the last call's uploads: [n] graphs | the LDS tier's list positions | the global tier's,
+  std::vector<uint32_t> lc_map;      // ... [K] candidate position -> live position (round 1's, then the later rounds'),
+  std::vector<uint32_t> lc_live;     // ... [K1] live position -> candidate position
+  DevBuf<uint32_t> d_lccand;         // [K] candidate position -> label
+  DevBuf<uint32_t> d_lcmap;          // [2 K] round 1's map (the identity) | the later rounds'
+  DevBuf<uint32_t> d_lclive;         // [K]
+  DevBuf<uint32_t> d_lckey;          // the table's keys
+  DevBuf<uint32_t> d_lcval;          // ... and candidate positions
+  DevBuf<uint32_t> d_lcdesc;         // [2 n]
+  DevBuf<uint64_t> d_lchit;          // [n][chunks] round 1's hit words
+  DevBuf<uint64_t> d_lcreg;          // the workgroups' regions: the hit list's rest, k_lc_glob's dead words
+  DevBuf<uint64_t> d_lcw[3];         // the rounds' cut words, one per chunk of 64 ranks (round 1: then the any-hit words)
+  DevBuf<uint64_t> d_lclost[3];      // the rounds' lost words [n][chunks]
+  DevBuf<uint32_t> d_lcscan;         // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
+  DevBuf<uint32_t> d_lcrows;         // [rows][4] nemo_label_cut, then [rows] n_lost
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -438,11 +463,12 @@ struct nemo_ctx {
   hipEvent_t ev_knock = nullptr;   // the knock-out calls' counts / rows have reached pinned memory
   hipEvent_t ev_cuts = nullptr;    // nemo_min_cuts' counts / words / totals / rows have reached pinned memory
   hipEvent_t ev_klabel = nullptr;  // nemo_knockout_labels' level counts / words / counts have reached pinned memory
-  hipEvent_t *const events[24] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_lcuts = nullptr;   // nemo_min_label_cuts' level counts / round 1's words / totals / rows have reached pinned memory
+  hipEvent_t *const events[25] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
-                                  &ev_cuts,    &ev_klabel};
+                                  &ev_cuts,    &ev_klabel,  &ev_lcuts};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -457,12 +483,13 @@ struct nemo_ctx {
   Pinned<uint32_t> h_knock;  // the knock-out calls: the listed graphs' (leaves, Kahn levels), then the rows
   Pinned<uint32_t> h_cuts;   // nemo_min_cuts: counts, round 1's words and the candidates, the totals, then the rows
   Pinned<uint64_t> h_klabel;  // nemo_knockout_labels: the level counts; then the (lost, hit) words and the counts
-  void **const pinned[25] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint32_t> h_lcuts;  // nemo_min_label_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
+  void **const pinned[26] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
-                             h_cuts.slot(),  h_klabel.slot()};
+                             h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;
@@ -627,6 +654,50 @@ static int timed_on(nemo_ctx *c, hipStream_t st, const char *name, double bytes,
 template <class F>
 static int timed(nemo_ctx *c, const char *name, double bytes, double edges, F &&f) {
   return timed_on(c, c->stream, name, bytes, edges, f);
+}
+
+// The outer timing group of a call (nemo_min_cuts, nemo_knockout_labels, nemo_min_label_cuts): every launch of the
+// call between one pair of events, reported under `name`.
+struct GroupTimer {
+  nemo_ctx *c;
+  const char *name;
+  hipEvent_t ta = nullptr;
+  GroupTimer(nemo_ctx *c_, const char *name_) : c(c_), name(name_) {
+    const bool on = c->timing && (c->tgroups.empty() || std::find(c->tgroups.begin(), c->tgroups.end(), name) != c->tgroups.end());
+    if (on) {
+      ta = get_event(c);
+      hipEventRecord(ta, c->stream);
+    }
+  }
+  void done(double bytes, double ops) {
+    if (!ta) return;
+    hipEvent_t tb = get_event(c);
+    hipEventRecord(tb, c->stream);
+    c->pending.push_back({name, ta, tb, bytes, ops});
+    ta = nullptr;
+  }
+  ~GroupTimer() {
+    if (ta) c->ev_pool.push_back(ta);
+  }
+};
+
+// `need` elements in each buffer of a group that grows together: each to the largest request so far, released
+// together and allocated in the given order, behind a wait for the stream (an earlier launch may still read them)
+template <class... B>
+static int grow_group(nemo_ctx *c, const uint64_t *need, B &...bufs) {
+  bool ok = true;
+  int i = 0;
+  ((ok = ok && bufs.p && need[i++] <= bufs.cap), ...);
+  if (ok) return NEMO_OK;
+  uint64_t cap[sizeof...(B)];
+  i = 0;
+  ((cap[i] = std::max<uint64_t>(need[i], bufs.cap), i++), ...);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  (bufs.release(c), ...);
+  int rc = NEMO_OK;
+  i = 0;
+  ((rc = rc ? rc : bufs.grow(c, cap[i++])), ...);
+  return rc;
 }
 
 // `stream` waits for the diff kernels queued on `aux` (see nemo_ctx::aux)

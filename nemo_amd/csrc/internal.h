@@ -236,6 +236,43 @@ void launch_kl_lds(const DevCorpus &c, const KlArgs &a, uint32_t grid, hipStream
 void launch_kl_glob(const DevCorpus &c, const KlArgs &a, uint32_t grid, hipStream_t s);
 void launch_kl_count(const KlArgs &a, hipStream_t s);
 
+// One round of nemo_min_label_cuts (k_lcuts.hip): the hypotheses are the sets of `size` live candidate positions in
+// colex rank order (cut_host.h), shared by every listed graph; one lost word per (list position, chunk of 64 ranks).
+struct LcArgs {
+  const uint32_t *cand;      // [n_cand] candidate position -> label
+  uint32_t n_cand;
+  uint32_t *key, *val;       // [slots] the call's table: label + 1 -> candidate position (klabel_host.h's hash)
+  uint64_t slots;
+  const uint32_t *lmap;      // [n_cand] candidate position -> live position of this round (UINT32_MAX: not live)
+  uint32_t k1;               // live positions of this round
+  uint32_t size;             // 1..3: the round
+  uint32_t n_hyp, n_chunks;
+  const uint32_t *graph;     // [n] list position -> graph
+  const uint32_t *pos;       // [n_tier] the launched tier's list positions
+  uint32_t n_tier;           // list positions of the launched tier
+  uint32_t parts;            // chunk ranges per graph (klabel::split)
+  uint32_t sinks;            // 1: only sink goals match (NEMO_KL_SINKS)
+  uint32_t lds_total;        // k_lc_lds: the launch's dynamic LDS; what the image leaves holds the hit list's head
+  uint64_t *region;          // [workgroups][region_words] the hit list's rest (and k_lc_glob's dead words)
+  uint64_t region_words;     // u64 per workgroup
+  uint64_t dead_words;       // k_lc_glob: dead words at the region's start (the hit list follows)
+  uint64_t *lost;            // [n][n_chunks] the round's lost words
+  uint64_t *hit;             // round 1: [n][n_chunks] hit words
+  uint32_t n, q;             // list positions of the call; a cut is lost on at least q of them
+  uint64_t *words;           // k_lc_reduce: [n_chunks] cut words (round 1: then [n_chunks] any-hit words)
+  const uint64_t *pairs;     // round 3: round 2's cut words
+  const uint32_t *scan;      // k_lc_support: [n_chunks + 1] the round's first rows (CutArgs::scan)
+  uint32_t n_rows;           // ... the round's rows
+  uint32_t *n_lost;          // ... [n_rows] lost_count of each
+};
+void launch_lc_table(const LcArgs &a, hipStream_t s);  // the table is zero
+// the workgroups of round `size`'s k_lc_lds resident on the device at lds_bytes of dynamic LDS (0: the query failed)
+uint32_t lc_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu);
+void launch_lc_lds(const DevCorpus &c, const LcArgs &a, uint32_t grid, hipStream_t s);  // a.lds_total bytes of LDS
+void launch_lc_glob(const DevCorpus &c, const LcArgs &a, uint32_t grid, hipStream_t s);
+void launch_lc_reduce(const LcArgs &a, hipStream_t s);
+void launch_lc_support(const LcArgs &a, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

@@ -45,6 +45,8 @@ KO_MASKS = 1  # NEMO_KO_MASKS
 # struct nemo_cut (nemo_fetch_min_cuts)
 CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (3,))])
 KL_SINKS = 1  # NEMO_KL_SINKS
+# struct nemo_label_cut (nemo_fetch_min_label_cuts)
+LABEL_CUT_DTYPE = np.dtype([("size", np.uint32), ("label", np.uint32, (3,))])
 
 
 def header_symbols() -> List[str]:
@@ -126,6 +128,9 @@ def lib():
             "nemo_knockout_labels": ([vp, vp, sz, i32, vp, vp, sz, u32], i32),
             "nemo_fetch_knockout_labels": ([vp, vp, vp, u64], i32),
             "nemo_fetch_knockout_label_counts": ([vp, vp, vp, u64], i32),
+            "nemo_min_label_cuts": ([vp, vp, sz, i32, vp, sz, u32, u32, u32], i32),
+            "nemo_fetch_min_label_cuts": ([vp, vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_min_label_cut_stats": ([vp, vp], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -453,6 +458,36 @@ class Engine:
         n_lost, n_hit = np.zeros(n_sets, np.uint32), np.zeros(n_sets, np.uint32)
         self._chk(self.L.nemo_fetch_knockout_label_counts(self.h, _p(n_lost), _p(n_hit), n_sets))
         return n_lost, n_hit
+
+    def min_label_cuts(self, iters: Sequence[int], cond: int, cand_labels: Sequence[int], max_size: int = 2, min_runs: int = 0,
+                       sinks_only: bool = False):
+        """nemo_min_label_cuts: all minimal sets of <= max_size (1..3) of the candidate labels whose loss defeats the
+        outcome on at least min_runs of the listed runs' pre (cond 0) or post (cond 1) graphs (0: on every list
+        position).  A set removes every node of a graph whose label it names (sinks_only: every sink goal).
+        Returns (rows, n_lost): rows a structured array (LABEL_CUT_DTYPE: size, label[3] in candidate-list order,
+        unused entries UINT32_MAX) sorted by (size, colex rank of the live positions), n_lost[k] the list positions
+        on which row k is lost; min_label_cut_stats() has the rounds' counts."""
+        it = np.ascontiguousarray(iters, dtype=np.uint32)
+        cand = np.ascontiguousarray(cand_labels, dtype=np.uint32)
+        keep = cand if len(cand) else np.zeros(1, np.uint32)  # an empty list is a list: never NULL
+        self._chk(self.L.nemo_min_label_cuts(self.h, _p(it), len(it), int(cond), _p(keep), len(cand), int(max_size), int(min_runs),
+                                             KL_SINKS if sinks_only else 0))
+        return self.min_label_cut_rows()
+
+    def min_label_cut_rows(self):
+        """nemo_fetch_min_label_cuts: (rows, n_lost) of the last min_label_cuts call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_min_label_cuts(self.h, None, None, 0, ctypes.byref(n)))
+        out, n_lost = np.zeros(n.value, LABEL_CUT_DTYPE), np.zeros(n.value, np.uint32)
+        self._chk(self.L.nemo_fetch_min_label_cuts(self.h, _p(out), _p(n_lost), len(out), ctypes.byref(n)))
+        return out, n_lost
+
+    def min_label_cut_stats(self) -> np.ndarray:
+        """nemo_fetch_min_label_cut_stats: a 3 x 3 u64 array, row s - 1 = (live candidates entering round s,
+        hypotheses evaluated, minimal cuts found)."""
+        out = np.zeros(9, np.uint64)
+        self._chk(self.L.nemo_fetch_min_label_cut_stats(self.h, _p(out)))
+        return out.reshape(3, 3)
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
         """nemo_goal_labels: [n, label...] of a run's goal labels into device memory."""
