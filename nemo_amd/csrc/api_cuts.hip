@@ -1,15 +1,6 @@
-// api_cuts.hip — nemo_min_cuts and its fetches (k_cuts.hip, cut_host.h; DESIGN.md §Minimal cut sets).
-#include "ctx.h"
-
-namespace {
-
-int cut_wait(nemo_ctx *c) {  // the copies queued so far have reached pinned memory
-  HIPCHK(c, hipEventRecord(c->ev_cuts, c->stream));
-  HIPCHK(c, hipEventSynchronize(c->ev_cuts));
-  return NEMO_OK;
-}
-
-}  // namespace
+// api_cuts.hip — nemo_min_cuts and its fetches (k_cuts.hip, cut_host.h; DESIGN.md §Minimal cut sets).  The rounds'
+// sizes and the rows (count, scan, totals, emit, copy, stats) are knock_api.h's, shared with api_lcuts.hip.
+#include "knock_api.h"
 
 extern "C" {
 
@@ -74,13 +65,13 @@ int nemo_min_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t *can
     const double b_leaves = 8.0 * (double)V + 12.0;
     if ((rc = timed(c, "k_ko_leaves", b_leaves, 0, [&] { nemo::launch_ko_leaves(cs.dc, ka, false, s); }))) return rc;
     nemo::launch_to_host(c->h_cuts.p, ka.cnt, 8, s);
-    if ((rc = cut_wait(c))) return rc;
+    if ((rc = wait_copied(c, c->ev_cuts))) return rc;
     K = c->h_cuts.p[0];
     L = c->h_cuts.p[1];
     bytes += b_leaves;
   } else {
     nemo::launch_to_host(c->h_cuts.p, cs.dc.nlev + g, 4, s);
-    if ((rc = cut_wait(c))) return rc;
+    if ((rc = wait_copied(c, c->ev_cuts))) return rc;
     L = c->h_cuts.p[0];
   }
   cs.cut_stats[0] = K;
@@ -150,23 +141,20 @@ int nemo_min_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t *can
     hc.add(c->h_cuts.p, cs.d_cutw[0].p, 8 * ck1);
     if (!cand) hc.add(c->h_cuts.p + 2 * ck1, cs.d_cutcand.p, 4 * K);
     nemo::launch_to_host_multi(hc, s);
-    if ((rc = cut_wait(c))) return rc;
+    if ((rc = wait_copied(c, c->ev_cuts))) return rc;
   }
   if (!cand) cs.cut_cand.assign(c->h_cuts.p + 2 * ck1, c->h_cuts.p + 2 * ck1 + K);
   std::vector<uint32_t> live = cuts::live_list(reinterpret_cast<const uint64_t *>(c->h_cuts.p), K);
   const uint64_t K1 = live.size();
-  uint64_t n_hyp[3] = {K, 0, 0};
-  for (uint32_t sz = 2; sz <= max_size; sz++) {  // per round, before the round's launch: K1 is known only now
-    if (!cuts::round_fits(K1, sz))
-      return fail(c, NEMO_ERR_LIMIT, "nemo_min_cuts: the sets of %u of %llu live candidates exceed 2^32 - 2 hypotheses: shorten the candidate list",
-                  sz, (unsigned long long)K1);
-    n_hyp[sz - 1] = cuts::round_hyps(K1, sz);
-  }
-  const uint64_t ck[3] = {ck1, cuts::chunks(n_hyp[1]), cuts::chunks(n_hyp[2])};
-  const uint64_t scan_off[3] = {0, ck[0] + 1, ck[0] + ck[1] + 2};
-  const uint64_t n_scan = ck[0] + ck[1] + ck[2] + 3;
+  CutRounds rd;
+  if ((rc = cut_rounds(K, K1, max_size, [&](uint64_t k, uint32_t sz) -> int {
+         if (cuts::round_fits(k, sz)) return NEMO_OK;
+         return fail(c, NEMO_ERR_LIMIT, "nemo_min_cuts: the sets of %u of %llu live candidates exceed 2^32 - 2 hypotheses: shorten the candidate list",
+                     sz, (unsigned long long)k);
+       }, &rd)))
+    return rc;
   {
-    const uint64_t need[3] = {ck[1], ck[2], n_scan + nemo::dx_scan_tiles((uint32_t)(std::max(ck[0], std::max(ck[1], ck[2])) + 1))};
+    const uint64_t need[3] = {rd.ck[1], rd.ck[2], rd.scan_need};
     if ((rc = grow_group(c, need, cs.d_cutw[1], cs.d_cutw[2], cs.d_cutscan))) return rc;
   }
   if (max_size >= 2 && K1) {
@@ -178,58 +166,13 @@ int nemo_min_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t *can
     HIPCHK(c, hipMemcpyAsync(cs.d_cutlive.p, cs.cut_live.data(), 2 * K1 * 4, hipMemcpyHostToDevice, s));
   }
   for (uint32_t k = 1; k < max_size; k++) {
-    a[k].n_hyp = (uint32_t)n_hyp[k], a[k].n_chunks = (uint32_t)ck[k];
+    a[k].n_hyp = (uint32_t)rd.n_hyp[k], a[k].n_chunks = (uint32_t)rd.ck[k];
     a[k].live = cs.d_cutlive.p, a[k].lnode = cs.d_cutlive.p + K1;
     a[k].words = cs.d_cutw[k].p, a[k].pairs = k == 2 ? cs.d_cutw[1].p : nullptr;
     if ((rc = sweep(a[k]))) return rc;
   }
-  // popcounts, their scans, the totals
-  uint32_t *tsum = cs.d_cutscan.p + n_scan;
-  nemo::HostCopies hc;
-  for (uint32_t k = 0; k < max_size; k++) {
-    if (!a[k].n_chunks) continue;
-    a[k].scan = cs.d_cutscan.p + scan_off[k];
-    const double b = 12.0 * a[k].n_chunks;
-    if ((rc = timed(c, "k_cut_count", b, 0, [&] { nemo::launch_cut_count(a[k], s); }))) return rc;
-    if ((rc = timed(c, "k_cut_scan", 16.0 * a[k].n_chunks, 0, [&] { nemo::launch_scan(a[k].scan, a[k].n_chunks + 1, tsum, s); })))
-      return rc;
-    bytes += b + 16.0 * a[k].n_chunks;
-    hc.add(c->h_cuts.p + k, a[k].scan + a[k].n_chunks, 4);
-  }
-  c->h_cuts.p[0] = c->h_cuts.p[1] = c->h_cuts.p[2] = 0;
-  nemo::launch_to_host_multi(hc, s);
-  if ((rc = cut_wait(c))) return rc;
-  const uint64_t found[3] = {c->h_cuts.p[0], c->h_cuts.p[1], c->h_cuts.p[2]};
-  const uint64_t rows = found[0] + found[1] + found[2];
-  if (rows) {
-    if (4 * rows > cs.d_cutrows.cap || !cs.d_cutrows.p) {
-      HIPCHK(c, hipStreamSynchronize(s));
-      if ((rc = cs.d_cutrows.grow(c, 4 * rows))) return rc;
-    }
-    if ((rc = c->h_cuts.grow(c, 4 * rows))) return rc;
-    uint64_t base = 0;
-    for (uint32_t k = 0; k < max_size; k++) {
-      if (!a[k].n_chunks || !found[k]) continue;
-      a[k].rows = cs.d_cutrows.p + 4 * base;
-      const double b = 12.0 * a[k].n_chunks + 16.0 * (double)found[k] + 8.0 * (k + 1) * (double)found[k];
-      if ((rc = timed(c, "k_cut_emit", b, 0, [&] { nemo::launch_cut_emit(a[k], s); }))) return rc;
-      bytes += b;
-      base += found[k];
-    }
-  }
-  timer.done(bytes, ops);
-  if (rows) {
-    nemo::launch_to_host(c->h_cuts.p, cs.d_cutrows.p, 16 * rows, s);
-    if ((rc = cut_wait(c))) return rc;
-  }
-  for (uint32_t k = 0; k < max_size; k++) {
-    cs.cut_stats[3 * k] = k ? K1 : K;
-    cs.cut_stats[3 * k + 1] = n_hyp[k];
-    cs.cut_stats[3 * k + 2] = found[k];
-  }
-  cs.cut_rows = rows;
-  cs.cut_done = true;
-  return NEMO_OK;
+  const CutOut out = {c->h_cuts, c->ev_cuts, cs.d_cutscan, cs.d_cutrows, 4, cs.cut_stats, &cs.cut_rows, &cs.cut_done};
+  return cut_rows(c, out, rd, a, max_size, timer, bytes, ops);
 }
 
 int nemo_fetch_min_cuts(nemo_ctx *c, nemo_cut *out, uint64_t cap, uint64_t *n_out) {

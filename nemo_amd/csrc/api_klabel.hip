@@ -1,42 +1,6 @@
 // api_klabel.hip — nemo_knockout_labels and its fetches (k_klabel.hip, klabel_host.h; DESIGN.md §Knock-out by label).
-#include "ctx.h"
-
-namespace {
-
-int kl_wait(nemo_ctx *c) {  // the copies queued so far have reached pinned memory
-  HIPCHK(c, hipEventRecord(c->ev_klabel, c->stream));
-  HIPCHK(c, hipEventSynchronize(c->ev_klabel));
-  return NEMO_OK;
-}
-
-// What a workgroup of k_kl_lds takes of a CU's LDS beside its dynamic part: the kernel's static LDS (80 bytes by the
-// compiler's report, profiles/r15_kernel_resources.txt), rounded up to whole allocation granules with one to spare.
-// A value too small cannot cost a resident workgroup: the second occupancy query below refuses the larger size then.
-#define KL_LDS_STATIC 512
-
-// The launch's dynamic LDS: the largest image, and whatever more a workgroup may take while as many of them stay
-// resident per CU (the hit list's head lives there).  *resident: those workgroups on the whole device.
-int kl_lds_total(nemo_ctx *c, uint32_t image, uint32_t *total, uint32_t *resident) {
-  const uint32_t n_cu = c->cs.dc.n_cu;
-  const bool list = c->opt.kl_hitlist;
-  const uint32_t base = nemo::kl_lds_resident(image, n_cu, list);
-  if (!base) return fail(c, NEMO_ERR_HIP, "nemo_knockout_labels: no workgroup of k_kl_lds is resident at %u bytes of LDS", image);
-  *total = image, *resident = base;
-  int per_cu_lds = 0;
-  if (hipDeviceGetAttribute(&per_cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, c->device) != hipSuccess) {
-    (void)hipGetLastError();
-    return NEMO_OK;
-  }
-  const uint32_t per_cu = base / n_cu;
-  if (!list) return NEMO_OK;  // no hit list: nothing to keep behind the image
-  const int64_t room = (int64_t)per_cu_lds / per_cu - KL_LDS_STATIC;
-  if (room <= (int64_t)image) return NEMO_OK;
-  const uint32_t more = (uint32_t)room & ~15u;
-  if (nemo::kl_lds_resident(more, n_cu, list) == base) *total = more;
-  return NEMO_OK;
-}
-
-}  // namespace
+// The level counts, the tier split and the launch's dynamic LDS are knock_api.h's, shared with api_lcuts.hip.
+#include "knock_api.h"
 
 extern "C" {
 
@@ -92,42 +56,22 @@ int nemo_knockout_labels(nemo_ctx *c, const uint32_t *iters, size_t n, int cond,
   }
   if ((rc = ensure_event(c, &c->ev_klabel))) return rc;
   hipStream_t s = c->stream;
-  if (cs.kl_nlev.empty()) {  // once per load: a function of the loaded graphs
-    if ((rc = c->h_klabel.grow(c, cs.G / 2 + 1))) return rc;
-    nemo::launch_to_host(c->h_klabel.p, cs.dc.nlev, 4ull * cs.G, s);
-    if ((rc = kl_wait(c))) return rc;
-    const uint32_t *lv = reinterpret_cast<const uint32_t *>(c->h_klabel.p);
-    cs.kl_nlev.assign(lv, lv + cs.G);
-  }
+  if ((rc = ensure_nlev(c, c->h_klabel, c->ev_klabel))) return rc;
   GroupTimer timer(c, "k_klabel");
   // the tiers, the launch's LDS and what a workgroup keeps in device memory
-  uint32_t n_lds = 0, n_glob = 0, image = 0;
-  uint64_t glob_v = 0;
-  for (size_t i = 0; i < n; i++) {
-    const uint32_t g = desc[i];
-    if (knock::lds_fits(cs.nv(g), cs.ne(g), cs.kl_nlev[g], c->opt.knock_lds_max)) {
-      n_lds++;
-      image = std::max(image, knock::knock_lds_bytes((uint32_t)cs.nv(g), (uint32_t)cs.ne(g), cs.kl_nlev[g]));
-    } else {
-      n_glob++;
-      glob_v = std::max(glob_v, cs.nv(g));
-    }
-  }
-  {
-    uint32_t l = 0, gl = 0;
-    for (size_t i = 0; i < n; i++) {
-      const uint32_t g = desc[i];
-      if (knock::lds_fits(cs.nv(g), cs.ne(g), cs.kl_nlev[g], c->opt.knock_lds_max)) desc[n + l++] = (uint32_t)i;
-      else desc[n + n_lds + gl++] = (uint32_t)i;
-    }
-  }
+  const Tiers tr = split_tiers(c, desc, n);
+  const uint32_t n_lds = tr.n_lds, n_glob = tr.n_glob;
+  const uint64_t glob_v = tr.glob_v;
   uint32_t lds_total = 0, res_lds = 1;
   uint64_t spill = 0;
   if (n_lds) {
-    if ((rc = kl_lds_total(c, image, &lds_total, &res_lds))) return rc;
+    const bool list = c->opt.kl_hitlist;  // no hit list: nothing to keep behind the image
+    if ((rc = ko_lds_total(c, "nemo_knockout_labels", "k_kl_lds", [&](uint32_t b) { return nemo::kl_lds_resident(b, cs.dc.n_cu, list); },
+                           tr.image, list ? UINT32_MAX : 0, KO_LDS_STATIC, &lds_total, &res_lds)))
+      return rc;
     for (size_t k = 0; k < n_lds; k++) {
       const uint32_t g = desc[desc[n + k]];
-      const uint64_t head = (lds_total - knock::knock_lds_bytes((uint32_t)cs.nv(g), (uint32_t)cs.ne(g), cs.kl_nlev[g])) / 8u;
+      const uint64_t head = (lds_total - tier_image(c, g)) / 8u;
       spill = std::max<uint64_t>(spill, cs.nv(g) > head ? cs.nv(g) - head : 0);
     }
   }
@@ -199,7 +143,7 @@ int nemo_knockout_labels(nemo_ctx *c, const uint32_t *iters, size_t n, int cond,
   if ((rc = timed(c, "k_kl_count", b_cnt, 0, [&] { nemo::launch_kl_count(a, s); }))) return rc;
   timer.done(bytes + b_cnt, ops);
   nemo::launch_to_host(c->h_klabel.p, cs.d_klout.p, 8 * out_words, s);
-  if ((rc = kl_wait(c))) return rc;
+  if ((rc = wait_copied(c, c->ev_klabel))) return rc;
   cs.kl_done = true;
   return NEMO_OK;
 }

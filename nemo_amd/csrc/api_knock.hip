@@ -1,29 +1,7 @@
 // api_knock.hip — nemo_knockout_leaves, nemo_knockout_sets and their fetches (k_knock.hip).
-#include "ctx.h"
+#include "knock_api.h"
 
 namespace {
-
-struct KoTimer {  // the outer group: every launch of the call between one pair of events
-  nemo_ctx *c;
-  hipEvent_t ta = nullptr;
-  explicit KoTimer(nemo_ctx *c_) : c(c_) {
-    const bool on = c->timing && (c->tgroups.empty() || std::find(c->tgroups.begin(), c->tgroups.end(), "k_knock") != c->tgroups.end());
-    if (on) {
-      ta = get_event(c);
-      hipEventRecord(ta, c->stream);
-    }
-  }
-  void done(double bytes, double ops) {
-    if (!ta) return;
-    hipEvent_t tb = get_event(c);
-    hipEventRecord(tb, c->stream);
-    c->pending.push_back({"k_knock", ta, tb, bytes, ops});
-    ta = nullptr;
-  }
-  ~KoTimer() {
-    if (ta) c->ev_pool.push_back(ta);
-  }
-};
 
 // what every knock-out entry point checks first; leaves the device set and the graphs whole
 int ko_enter(nemo_ctx *c, const char *who, int cond, uint32_t flags) {
@@ -47,29 +25,20 @@ int ko_limit(nemo_ctx *c, const char *who, const knock::Totals &t) {
               who, (unsigned long long)t.n_chunks);
 }
 
-// The five per-hypothesis buffers grow as one group, each to the largest request so far, in a fixed order.
-int ko_grow(nemo_ctx *c, uint64_t n_leaf, uint64_t n_chunk32, uint64_t n_setoff, uint64_t n_rows, uint64_t n_dead) {
+// The five per-hypothesis buffers grow as one group (ctx.h's grow_group), each to the largest request so far, in
+// this order.  The leaves are none when every set is empty, the dead words when no chunk keeps them: one element
+// then, so that such a call finds the group grown.
+int ko_buffers(nemo_ctx *c, uint64_t n_leaf, uint64_t n_setoff, const knock::Totals &tot) {
   CorpusState &cs = c->cs;
-  const uint64_t need[5] = {n_leaf, n_chunk32, n_setoff, n_rows, n_dead};
-  if (need[0] <= cs.d_koleaf.cap && need[1] <= cs.d_kochunk.cap && need[2] <= cs.d_koset.cap && need[3] <= cs.d_korows.cap &&
-      need[4] <= cs.d_kodead.cap && cs.d_kodead.p)
-    return NEMO_OK;
-  const uint64_t cap[5] = {std::max(need[0], cs.d_koleaf.cap), std::max(need[1], cs.d_kochunk.cap),
-                           std::max(need[2], cs.d_koset.cap), std::max(need[3], cs.d_korows.cap),
-                           std::max(need[4], cs.d_kodead.cap)};
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier call's mask fetch may still read them
-  cs.d_koleaf.release(c), cs.d_kochunk.release(c), cs.d_koset.release(c), cs.d_korows.release(c), cs.d_kodead.release(c);
-  int rc;
-  if ((rc = cs.d_koleaf.grow(c, cap[0])) || (rc = cs.d_kochunk.grow(c, cap[1])) || (rc = cs.d_koset.grow(c, cap[2])) ||
-      (rc = cs.d_korows.grow(c, cap[3])) || (rc = cs.d_kodead.grow(c, cap[4])))
-    return rc;
-  return NEMO_OK;
+  const uint64_t need[5] = {std::max<uint64_t>(n_leaf, 1), tot.n_chunks + (tot.n_chunks + 7) / 8, n_setoff, 5 * tot.n_hyp,
+                            std::max<uint64_t>(tot.dead, 1)};
+  return grow_group(c, need, cs.d_koleaf, cs.d_kochunk, cs.d_koset, cs.d_korows, cs.d_kodead);
 }
 
 // The sweep of a call whose table, leaves / sets and buffers are in place: both tiers, the rows to pinned
 // memory, and the wait for them.  set_nodes: the nodes the sets name in all (sets mode).
 int ko_sweep(nemo_ctx *c, nemo::KnockArgs &a, const std::vector<knock::GraphIn> &in, const std::vector<uint32_t> &levels,
-             uint64_t set_nodes, KoTimer &timer, double bytes_before) {
+             uint64_t set_nodes, GroupTimer &timer, double bytes_before) {
   CorpusState &cs = c->cs;
   const knock::Table &t = cs.ko_tab;
   hipStream_t s = c->stream;
@@ -105,8 +74,7 @@ int ko_sweep(nemo_ctx *c, nemo::KnockArgs &a, const std::vector<knock::GraphIn> 
     return rc;
   timer.done(bytes_before + b_tier[0] + b_tier[1], ops[0] + ops[1]);
   nemo::launch_to_host(c->h_knock.p, cs.d_korows.p, 20 * t.tot.n_hyp, s);  // the rows to pinned memory
-  HIPCHK(c, hipEventRecord(c->ev_knock, s));
-  HIPCHK(c, hipEventSynchronize(c->ev_knock));
+  if ((rc = wait_copied(c, c->ev_knock))) return rc;
   cs.ko_done = true;
   return NEMO_OK;
 }
@@ -142,7 +110,7 @@ int nemo_knockout_leaves(nemo_ctx *c, const uint32_t *iters, size_t n, int cond,
   if ((rc = ensure_event(c, &c->ev_knock))) return rc;
   if ((rc = c->h_knock.grow(c, 2 * (uint64_t)n))) return rc;
   hipStream_t s = c->stream;
-  KoTimer timer(c);
+  GroupTimer timer(c, "k_knock");
   if (4 * (uint64_t)n + 1 > cs.d_kocnt.cap || !cs.d_kocnt.p) {
     HIPCHK(c, hipStreamSynchronize(s));
     if ((rc = cs.d_kocnt.grow(c, 4 * (uint64_t)n + 1))) return rc;
@@ -158,8 +126,7 @@ int nemo_knockout_leaves(nemo_ctx *c, const uint32_t *iters, size_t n, int cond,
   const double b_leaves = 8.0 * nodes + 12.0 * (double)n;  // node word + row pointer of every node; the counts
   if ((rc = timed(c, "k_ko_leaves", b_leaves, 0, [&] { nemo::launch_ko_leaves(cs.dc, a, false, s); }))) return rc;
   nemo::launch_to_host(c->h_knock.p, a.cnt, 8 * (uint64_t)n, s);
-  HIPCHK(c, hipEventRecord(c->ev_knock, s));
-  HIPCHK(c, hipEventSynchronize(c->ev_knock));
+  if ((rc = wait_copied(c, c->ev_knock))) return rc;
   std::vector<knock::GraphIn> in(n);
   std::vector<uint32_t> levels(n);
   for (size_t i = 0; i < n; i++) {
@@ -179,7 +146,7 @@ int nemo_knockout_leaves(nemo_ctx *c, const uint32_t *iters, size_t n, int cond,
     return NEMO_OK;
   }
   if ((rc = c->h_knock.grow(c, 5 * tot.n_hyp))) return rc;
-  if ((rc = ko_grow(c, tot.n_hyp, tot.n_chunks + (tot.n_chunks + 7) / 8, 1, 5 * tot.n_hyp, tot.dead))) return rc;
+  if ((rc = ko_buffers(c, tot.n_hyp, 1, tot))) return rc;
   HIPCHK(c, hipMemcpyAsync(cs.d_kocnt.p + n, desc.data() + n, (n + 1) * 4, hipMemcpyHostToDevice, s));
   a.leaf = cs.d_koleaf.p;
   a.set_off = nullptr;
@@ -230,10 +197,9 @@ int nemo_knockout_sets(nemo_ctx *c, uint32_t iteration, int cond, const uint64_t
   if ((rc = ensure_event(c, &c->ev_knock))) return rc;
   if ((rc = c->h_knock.grow(c, std::max<uint64_t>(4, 5 * (uint64_t)n_sets)))) return rc;
   hipStream_t s = c->stream;
-  KoTimer timer(c);
+  GroupTimer timer(c, "k_knock");
   nemo::launch_to_host(c->h_knock.p, cs.dc.nlev + g, 4, s);
-  HIPCHK(c, hipEventRecord(c->ev_knock, s));
-  HIPCHK(c, hipEventSynchronize(c->ev_knock));
+  if ((rc = wait_copied(c, c->ev_knock))) return rc;
   std::vector<knock::GraphIn> in(1);
   std::vector<uint32_t> levels(1, c->h_knock.p[0]);
   in[0] = {g, V, n_sets, knock::lds_fits(V, cs.ne(g), levels[0], c->opt.knock_lds_max)};
@@ -241,7 +207,7 @@ int nemo_knockout_sets(nemo_ctx *c, uint32_t iteration, int cond, const uint64_t
   if (tot.limit != knock::LIMIT_OK) return ko_limit(c, "nemo_knockout_sets", tot);
   cs.ko_tab = knock::chunk_table(in.data(), 1, cs.ko_masks);
   const uint64_t n_nodes = set_off[n_sets] - set_off[0];
-  if ((rc = ko_grow(c, n_nodes, tot.n_chunks + (tot.n_chunks + 7) / 8, n_sets + 1, 5 * tot.n_hyp, tot.dead))) return rc;
+  if ((rc = ko_buffers(c, n_nodes, n_sets + 1, tot))) return rc;
   std::vector<uint64_t> &off = cs.ko_setoff;  // relative to the first set
   off.resize(n_sets + 1);
   for (size_t k = 0; k <= n_sets; k++) off[k] = set_off[k] - set_off[0];

@@ -1,39 +1,9 @@
 // api_lcuts.hip — nemo_min_label_cuts and its fetches (k_lcuts.hip, lcut_host.h; DESIGN.md §Minimal cut sets by label).
-#include "ctx.h"
+// knock_api.h holds what it shares with api_klabel.hip (the level counts, the tier split, a round's dynamic LDS) and
+// with api_cuts.hip (the rounds' sizes and the rows).
+#include "knock_api.h"
 
 namespace {
-
-int lc_wait(nemo_ctx *c) {  // the copies queued so far have reached pinned memory
-  HIPCHK(c, hipEventRecord(c->ev_lcuts, c->stream));
-  HIPCHK(c, hipEventSynchronize(c->ev_lcuts));
-  return NEMO_OK;
-}
-
-// What a workgroup of k_lc_lds takes of a CU's LDS beside its dynamic part: the kernel's static LDS (48 bytes by the
-// compiler's report), rounded up to whole allocation granules with one to spare.  A value too small cannot cost a
-// resident workgroup: the second occupancy query below refuses the larger size then.
-#define LC_LDS_STATIC 512
-
-// Round `size`'s dynamic LDS: the largest image plus the `list` bytes of the longest hit list behind it, as far as
-// a workgroup may take them while as many workgroups stay resident per CU; what does not fit goes to the workgroup's
-// region.  *resident: those workgroups on the whole device.  (The residency query raises the kernel's
-// MaxDynamicSharedMemorySize, a permission, not an allocation; launch_lc_lds sets it to the launch's size.)
-int lc_lds_total(nemo_ctx *c, uint32_t size, uint32_t image, uint64_t list, uint32_t *total, uint32_t *resident) {
-  const uint32_t n_cu = c->cs.dc.n_cu;
-  const uint32_t base = nemo::lc_lds_resident(size, image, n_cu);
-  if (!base) return fail(c, NEMO_ERR_HIP, "nemo_min_label_cuts: no workgroup of k_lc_lds is resident at %u bytes of LDS", image);
-  *total = image, *resident = base;
-  int per_cu_lds = 0;
-  if (hipDeviceGetAttribute(&per_cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, c->device) != hipSuccess) {
-    (void)hipGetLastError();
-    return NEMO_OK;
-  }
-  const int64_t room = (int64_t)per_cu_lds / (base / n_cu) - LC_LDS_STATIC;
-  if (room <= (int64_t)image) return NEMO_OK;
-  const uint32_t more = (uint32_t)std::min<uint64_t>((uint64_t)room & ~15ull, image + ((list + 15) & ~15ull));
-  if (more > image && nemo::lc_lds_resident(size, more, n_cu) == base) *total = more;
-  return NEMO_OK;
-}
 
 struct LcPlan {  // one round's launches
   uint32_t lds_total = 0;
@@ -115,29 +85,12 @@ int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, 
   }
   if ((rc = ensure_event(c, &c->ev_lcuts))) return rc;
   hipStream_t s = c->stream;
-  if (cs.kl_nlev.empty()) {  // once per load: a function of the loaded graphs (shared with nemo_knockout_labels)
-    if ((rc = c->h_lcuts.grow(c, cs.G + 8))) return rc;
-    nemo::launch_to_host(c->h_lcuts.p, cs.dc.nlev, 4ull * cs.G, s);
-    if ((rc = lc_wait(c))) return rc;
-    cs.kl_nlev.assign(c->h_lcuts.p, c->h_lcuts.p + cs.G);
-  }
+  if ((rc = ensure_nlev(c, c->h_lcuts, c->ev_lcuts))) return rc;  // (shared with nemo_knockout_labels)
   GroupTimer timer(c, "k_lcuts");
   // the tiers, the rounds' LDS and what a workgroup keeps in device memory
-  auto fits = [&](uint32_t g) { return knock::lds_fits(cs.nv(g), cs.ne(g), cs.kl_nlev[g], c->opt.knock_lds_max); };
-  auto image_of = [&](uint32_t g) { return knock::knock_lds_bytes((uint32_t)cs.nv(g), (uint32_t)cs.ne(g), cs.kl_nlev[g]); };
-  uint32_t n_lds = 0, n_glob = 0, image = 0;
-  uint64_t glob_v = 0, lds_v = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (fits(desc[i])) n_lds++, image = std::max(image, image_of(desc[i])), lds_v = std::max(lds_v, cs.nv(desc[i]));
-    else n_glob++, glob_v = std::max(glob_v, cs.nv(desc[i]));
-  }
-  {
-    uint32_t l = 0, gl = 0;
-    for (size_t i = 0; i < n; i++) {
-      if (fits(desc[i])) desc[n + l++] = (uint32_t)i;
-      else desc[n + n_lds + gl++] = (uint32_t)i;
-    }
-  }
+  const Tiers tr = split_tiers(c, desc, n);
+  const uint32_t n_lds = tr.n_lds, n_glob = tr.n_glob;
+  const uint64_t glob_v = tr.glob_v;
   const uint32_t cap = c->opt.kl_grid;
   LcPlan plan[3];
   uint64_t reg_need = 1;
@@ -145,10 +98,12 @@ int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, 
     LcPlan &p = plan[sz - 1];
     uint32_t res_lds = 1;
     if (n_lds) {
-      if ((rc = lc_lds_total(c, sz, image, 4 * lcuts::list_entries(K, lds_v), &p.lds_total, &res_lds))) return rc;
+      if ((rc = ko_lds_total(c, "nemo_min_label_cuts", "k_lc_lds", [&](uint32_t b) { return nemo::lc_lds_resident(sz, b, cs.dc.n_cu); },
+                             tr.image, 4 * lcuts::list_entries(K, tr.lds_v), KO_LDS_STATIC, &p.lds_total, &res_lds)))
+        return rc;
       for (size_t k = 0; k < n_lds; k++) {
         const uint32_t g = desc[desc[n + k]];
-        p.rw_lds = std::max(p.rw_lds, lcuts::region_words(0, lcuts::list_entries(K, cs.nv(g)), (p.lds_total - image_of(g)) / 4u));
+        p.rw_lds = std::max(p.rw_lds, lcuts::region_words(0, lcuts::list_entries(K, cs.nv(g)), (p.lds_total - tier_image(c, g)) / 4u));
       }
     }
     p.rw_glob = lcuts::region_words(knock::dead_words(glob_v), lcuts::list_entries(K, glob_v), 0);
@@ -226,21 +181,14 @@ int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, 
   a[0].lost = cs.d_lclost[0].p, a[0].words = cs.d_lcw[0].p;
   if ((rc = round(a[0]))) return rc;
   nemo::launch_to_host(c->h_lcuts.p, cs.d_lcw[0].p, 16 * ck1, s);
-  if ((rc = lc_wait(c))) return rc;
+  if ((rc = wait_copied(c, c->ev_lcuts))) return rc;
   const uint64_t *w1 = reinterpret_cast<const uint64_t *>(c->h_lcuts.p);
   cs.lc_live = lcuts::live_list(w1, w1 + ck1, K);
   const uint64_t K1 = cs.lc_live.size();
-  uint64_t n_hyp[3] = {K, 0, 0};
-  for (uint32_t sz = 2; sz <= max_size; sz++) {  // per round, before the round's launch: K1 is known only now
-    if ((rc = limit(K1, sz))) return rc;
-    n_hyp[sz - 1] = cuts::round_hyps(K1, sz);
-  }
-  const uint64_t ck[3] = {ck1, cuts::chunks(n_hyp[1]), cuts::chunks(n_hyp[2])};
-  const uint64_t scan_off[3] = {0, ck[0] + 1, ck[0] + ck[1] + 2};
-  const uint64_t n_scan = ck[0] + ck[1] + ck[2] + 3;
+  CutRounds rd;
+  if ((rc = cut_rounds(K, K1, max_size, limit, &rd))) return rc;
   {
-    const uint64_t need[5] = {ck[1], ck[2], (uint64_t)n * ck[1], (uint64_t)n * ck[2],
-                              n_scan + nemo::dx_scan_tiles((uint32_t)(std::max(ck[0], std::max(ck[1], ck[2])) + 1))};
+    const uint64_t need[5] = {rd.ck[1], rd.ck[2], (uint64_t)n * rd.ck[1], (uint64_t)n * rd.ck[2], rd.scan_need};
     if ((rc = grow_group(c, need, cs.d_lcw[1], cs.d_lcw[2], cs.d_lclost[1], cs.d_lclost[2], cs.d_lcscan))) return rc;
   }
   if (max_size >= 2 && K1) {
@@ -250,63 +198,23 @@ int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, 
     HIPCHK(c, hipMemcpyAsync(cs.d_lclive.p, cs.lc_live.data(), K1 * 4, hipMemcpyHostToDevice, s));
   }
   for (uint32_t k = 1; k < max_size; k++) {
-    a[k].lmap = cs.d_lcmap.p + K, a[k].k1 = (uint32_t)K1, a[k].n_hyp = (uint32_t)n_hyp[k], a[k].n_chunks = (uint32_t)ck[k];
+    a[k].lmap = cs.d_lcmap.p + K, a[k].k1 = (uint32_t)K1, a[k].n_hyp = (uint32_t)rd.n_hyp[k], a[k].n_chunks = (uint32_t)rd.ck[k];
     a[k].lost = cs.d_lclost[k].p, a[k].words = cs.d_lcw[k].p, a[k].pairs = k == 2 ? cs.d_lcw[1].p : nullptr;
     if ((rc = round(a[k]))) return rc;
   }
-  // popcounts, their scans, the totals: k_cuts.hip's row kernels over the cut words
+  // the rows: k_cuts.hip's row kernels over the cut words, and behind a round's emit the recount of its rows' support
   nemo::CutArgs e[3] = {};
-  uint32_t *tsum = cs.d_lcscan.p + n_scan;
-  nemo::HostCopies hc;
   for (uint32_t k = 0; k < max_size; k++) {
-    if (!a[k].n_chunks) continue;
     e[k].size = k + 1, e[k].n_hyp = a[k].n_hyp, e[k].n_chunks = a[k].n_chunks, e[k].words = a[k].words;
     e[k].cand = cs.d_lccand.p, e[k].live = k ? cs.d_lclive.p : nullptr;
-    e[k].scan = cs.d_lcscan.p + scan_off[k];
-    const double b = 12.0 * e[k].n_chunks;
-    if ((rc = timed(c, "k_cut_count", b, 0, [&] { nemo::launch_cut_count(e[k], s); }))) return rc;
-    if ((rc = timed(c, "k_cut_scan", 16.0 * e[k].n_chunks, 0, [&] { nemo::launch_scan(e[k].scan, e[k].n_chunks + 1, tsum, s); })))
-      return rc;
-    bytes += b + 16.0 * e[k].n_chunks;
-    hc.add(c->h_lcuts.p + k, e[k].scan + e[k].n_chunks, 4);
   }
-  c->h_lcuts.p[0] = c->h_lcuts.p[1] = c->h_lcuts.p[2] = 0;
-  nemo::launch_to_host_multi(hc, s);
-  if ((rc = lc_wait(c))) return rc;
-  const uint64_t found[3] = {c->h_lcuts.p[0], c->h_lcuts.p[1], c->h_lcuts.p[2]};
-  const uint64_t rows = found[0] + found[1] + found[2];
-  if (rows) {
-    if (5 * rows > cs.d_lcrows.cap || !cs.d_lcrows.p) {
-      HIPCHK(c, hipStreamSynchronize(s));
-      if ((rc = cs.d_lcrows.grow(c, 5 * rows))) return rc;
-    }
-    if ((rc = c->h_lcuts.grow(c, 5 * rows))) return rc;
-    uint64_t base = 0;
-    for (uint32_t k = 0; k < max_size; k++) {
-      if (!a[k].n_chunks || !found[k]) continue;
-      e[k].rows = cs.d_lcrows.p + 4 * base;
-      const double b = 12.0 * e[k].n_chunks + 16.0 * (double)found[k] + 8.0 * (k + 1) * (double)found[k];
-      if ((rc = timed(c, "k_cut_emit", b, 0, [&] { nemo::launch_cut_emit(e[k], s); }))) return rc;
-      a[k].scan = e[k].scan, a[k].n_rows = (uint32_t)found[k], a[k].n_lost = cs.d_lcrows.p + 4 * rows + base;
-      const double b_sup = (double)found[k] * (8.0 * (double)n + 16.0);
-      if ((rc = timed(c, "k_lc_support", b_sup, 0, [&] { nemo::launch_lc_support(a[k], s); }))) return rc;
-      bytes += b + b_sup;
-      base += found[k];
-    }
-  }
-  timer.done(bytes, ops);
-  if (rows) {
-    nemo::launch_to_host(c->h_lcuts.p, cs.d_lcrows.p, 20 * rows, s);
-    if ((rc = lc_wait(c))) return rc;
-  }
-  for (uint32_t k = 0; k < max_size; k++) {
-    cs.lc_stats[3 * k] = k ? K1 : K;
-    cs.lc_stats[3 * k + 1] = n_hyp[k];
-    cs.lc_stats[3 * k + 2] = found[k];
-  }
-  cs.lc_rows = rows;
-  cs.lc_done = true;
-  return NEMO_OK;
+  const CutOut out = {c->h_lcuts, c->ev_lcuts, cs.d_lcscan, cs.d_lcrows, 5, cs.lc_stats, &cs.lc_rows, &cs.lc_done};
+  return cut_rows(c, out, rd, e, max_size, timer, bytes, ops, [&](uint32_t k, uint64_t found, uint64_t base, uint64_t rows, double *total) {
+    a[k].scan = e[k].scan, a[k].n_rows = (uint32_t)found, a[k].n_lost = cs.d_lcrows.p + 4 * rows + base;
+    const double b_sup = (double)found * (8.0 * (double)n + 16.0);
+    *total += b_sup;
+    return timed(c, "k_lc_support", b_sup, 0, [&] { nemo::launch_lc_support(a[k], s); });
+  });
 }
 
 int nemo_fetch_min_label_cuts(nemo_ctx *c, nemo_label_cut *out, uint32_t *n_lost, uint64_t cap, uint64_t *n_out) {

@@ -656,8 +656,8 @@ static int timed(nemo_ctx *c, const char *name, double bytes, double edges, F &&
   return timed_on(c, c->stream, name, bytes, edges, f);
 }
 
-// The outer timing group of a call (nemo_min_cuts, nemo_knockout_labels, nemo_min_label_cuts): every launch of the
-// call between one pair of events, reported under `name`.
+// The outer timing group of a call (the knock-out family's: knock_api.h): every launch of the call between one pair
+// of events, reported under `name`.
 struct GroupTimer {
   nemo_ctx *c;
   const char *name;

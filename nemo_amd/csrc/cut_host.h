@@ -1,6 +1,7 @@
 // cut_host.h — the arithmetic of nemo_min_cuts (k_cuts.hip; DESIGN.md §Minimal cut sets) as pure functions: the
 // colex rank of a pair / triple of live positions and its inverse (the kernels call the very same code), the
-// per-round limit, the validation of the candidate list, the live list from round 1's words, and the chunk and
+// round-3 test for a cut pair inside a triple (k_cuts.hip and k_lcuts.hip call the very same code), the per-round
+// limit, the validation of the candidate list, the live list from round 1's words, and the chunk and
 // grid counts.  No HIP and no context, so tools/cut_host_check.cpp drives it under the host sanitizers.
 #pragma once
 #include <math.h>
@@ -60,6 +61,14 @@ KO_HD static inline Pos unrank(uint64_t h) {
   if (SIZE == 2u) unrank2(h, &p.a, &p.b);
   if (SIZE == 3u) unrank3(h, &p.a, &p.b, &p.c);
   return p;
+}
+
+// Round 3's test "a pair of this triple is already a cut": pairs are round 2's words, bit rank2(x, y) of them =
+// "live positions x < y are a cut"; such a triple is no minimal cut.
+KO_HD static inline bool has_cut_pair(const uint64_t *pairs, const Pos &p) {
+  const uint64_t r0 = rank2(p.a, p.b), r1 = rank2(p.a, p.c), r2 = rank2(p.b, p.c);
+  const uint64_t w0 = pairs[r0 >> 6], w1 = pairs[r1 >> 6], w2 = pairs[r2 >> 6];
+  return (((w0 >> (r0 & 63u)) | (w1 >> (r1 & 63u)) | (w2 >> (r2 & 63u))) & 1ull) != 0ull;
 }
 
 // hypotheses of round `size` (1..3) over k live candidates; CUT_SAT where the count does not fit

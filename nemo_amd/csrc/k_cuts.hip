@@ -2,7 +2,8 @@
 // graph read as an AND/OR circuit.  A round's hypotheses are the sets of 1, 2 or 3 live candidates in colex rank
 // order (cut_host.h), so a workgroup makes the seeds of a chunk of 64 hypotheses from the chunk's index alone.
 // k_cut_lds is the persistent form of k_ko_lds: it stages the graph's LDS image once and loops over chunks,
-// running the knock-out sweep (ko_sweep.h) on each; a chunk's result is one word, the AND of the root words.
+// running the knock-out sweep on each; a chunk's result is one word, the AND of the root words (the zeroing, the
+// sweep and the lost word: ko_sweep.h; round 3's cut-pair test: cut_host.h).
 // k_cut_glob is the same loop over the CSR in device memory.  k_cut_count / k_cut_emit turn the rounds' words
 // into nemo_cut rows in (size, rank) order.
 #include "cut_host.h"
@@ -18,13 +19,9 @@ __device__ __forceinline__ void cut_loop(const CutArgs &a, const KoImg<LDS> &g) 
   __shared__ uint64_t s_and[KO_BLOCK / 64];
   const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
   uint64_t *dead = g.dead;
-  uint4 *z = reinterpret_cast<uint4 *>(dead);
-  const uint32_t pairs = (g.V + 1u) / 2u;
   for (uint32_t ci = blockIdx.x; ci < a.n_chunks; ci += gridDim.x) {
     // the previous chunk's words go (its last reads lie behind the barrier that ends the loop body)
-    for (uint32_t i = tid; i < pairs; i += KO_BLOCK) z[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (!LDS) __threadfence_block();
-    __syncthreads();
+    ko_zero_dead<LDS>(g);
     const uint32_t first = ci * KO_CHUNK, n = min(KO_CHUNK, a.n_hyp - first);
     // seeds: lane t's hypothesis is the set of rank first + t; hypotheses of one chunk share nodes
     bool sub = false;  // round 3: one of the set's pairs is a cut already
@@ -36,26 +33,15 @@ __device__ __forceinline__ void cut_loop(const CutArgs &a, const KoImg<LDS> &g) 
       if (va < g.V) atomicOr(&d64[va], (unsigned long long)bit);
       if (SIZE >= 2u && vb < g.V) atomicOr(&d64[vb], (unsigned long long)bit);
       if (SIZE >= 3u && vc < g.V) atomicOr(&d64[vc], (unsigned long long)bit);
-      if (SIZE == 3u) {  // the three pairs' bits of round 2's words, read while the sweep runs
-        const uint64_t r0 = cuts::rank2(p.a, p.b), r1 = cuts::rank2(p.a, p.c), r2 = cuts::rank2(p.b, p.c);
-        const uint64_t w0 = a.pairs[r0 >> 6], w1 = a.pairs[r1 >> 6], w2 = a.pairs[r2 >> 6];
-        sub = (((w0 >> (r0 & 63u)) | (w1 >> (r1 & 63u)) | (w2 >> (r2 & 63u))) & 1ull) != 0ull;
-      }
+      if (SIZE == 3u) sub = cuts::has_cut_pair(a.pairs, p);  // round 2's words, read while the sweep runs
     }
     if (!LDS) __threadfence_block();
     __syncthreads();
     ko_sweep<LDS>(g);
-    // lost: every root dead, per bit column (the level offsets are staged: read behind a barrier)
-    const uint32_t n_roots = g.L ? (uint32_t)g.lvl[1] : 0u;
-    uint64_t w = ~0ull;
-    for (uint32_t i = tid; i < n_roots; i += KO_BLOCK) w &= dead[g.topo[i]];
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) w &= (uint64_t)__shfl_xor((unsigned long long)w, dd);
-    if (lane == 0) s_and[wave] = w;
-    __syncthreads();
+    // lost: every root dead, per bit column.  Every thread holds the word; wave 0, whose lanes hold the chunk's
+    // `sub`, finishes.  (s_and is written next behind the next chunk's barriers.)
+    uint64_t lost = ko_lost_word<LDS>(g, n, s_and);
     if (wave == 0) {
-      uint64_t lost = n_roots ? (s_and[0] & s_and[1] & s_and[2] & s_and[3]) : 0ull;
-      lost &= n == KO_CHUNK ? ~0ull : (1ull << n) - 1ull;
       if (SIZE == 3u) lost &= ~__ballot(sub);
       if (lane == 0) a.words[ci] = lost;
     }
@@ -66,8 +52,7 @@ __device__ __forceinline__ void cut_loop(const CutArgs &a, const KoImg<LDS> &g) 
 template <uint32_t SIZE>
 __global__ __launch_bounds__(KO_BLOCK) void k_cut_lds(DevCorpus c, CutArgs a) {
   extern __shared__ __align__(16) uint8_t dyn[];
-  const GraphView gv = c.view(a.graph);
-  const KoImg<true> g = ko_stage_image(gv, dyn);  // once; the loop's first barrier ends the staging
+  const KoImg<true> g = ko_stage_image(c.view(a.graph), dyn);  // once; the loop's first barrier ends the staging
   cut_loop<true, SIZE>(a, g);
 }
 
@@ -75,10 +60,7 @@ __global__ __launch_bounds__(KO_BLOCK) void k_cut_lds(DevCorpus c, CutArgs a) {
 template <uint32_t SIZE>
 __global__ __launch_bounds__(KO_BLOCK) void k_cut_glob(DevCorpus c, CutArgs a) {
   const GraphView gv = c.view(a.graph);
-  KoImg<false> g;
-  g.fp = gv.fp, g.fc = gv.fc, g.topo = gv.topo, g.lvl = gv.lvl, g.rule = nullptr, g.word = gv.word;
-  g.dead = a.dead + (uint64_t)blockIdx.x * (((uint64_t)gv.V + 1ull) & ~1ull);
-  g.V = gv.V, g.L = gv.nlev;
+  const KoImg<false> g = ko_glob_image(gv, a.dead + (uint64_t)blockIdx.x * (((uint64_t)gv.V + 1ull) & ~1ull));
   cut_loop<false, SIZE>(a, g);
 }
 
@@ -105,33 +87,20 @@ __global__ __launch_bounds__(KO_BLOCK) void k_cut_emit(CutArgs a) {
   reinterpret_cast<uint4 *>(a.rows)[r] = row;
 }
 
-static const void *cut_lds_kernel(uint32_t size) {
-  return size == 1u ? (const void *)k_cut_lds<1> : size == 2u ? (const void *)k_cut_lds<2> : (const void *)k_cut_lds<3>;
-}
-
 uint32_t cut_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu) {
-  int per_cu = 0;
-  const void *f = cut_lds_kernel(size);
-  if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, KO_BLOCK, lds_bytes) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    return 0u;
-  }
-  return (uint32_t)per_cu * n_cu;
+  const void *f = nullptr;
+  ko_by_size(size, [&](auto sz) { f = (const void *)k_cut_lds<decltype(sz)::value>; });
+  return ko_lds_resident(f, lds_bytes, n_cu);
 }
 
 void launch_cut_lds(const DevCorpus &c, const CutArgs &a, uint32_t grid, uint32_t lds_bytes, hipStream_t s) {
   if (!a.n_chunks) return;
-  if (a.size == 1u) hipLaunchKernelGGL(k_cut_lds<1>, dim3(grid), dim3(KO_BLOCK), lds_bytes, s, c, a);
-  else if (a.size == 2u) hipLaunchKernelGGL(k_cut_lds<2>, dim3(grid), dim3(KO_BLOCK), lds_bytes, s, c, a);
-  else hipLaunchKernelGGL(k_cut_lds<3>, dim3(grid), dim3(KO_BLOCK), lds_bytes, s, c, a);
+  ko_by_size(a.size, [&](auto sz) { hipLaunchKernelGGL(k_cut_lds<decltype(sz)::value>, dim3(grid), dim3(KO_BLOCK), lds_bytes, s, c, a); });
 }
 
 void launch_cut_glob(const DevCorpus &c, const CutArgs &a, uint32_t grid, hipStream_t s) {
   if (!a.n_chunks) return;
-  if (a.size == 1u) hipLaunchKernelGGL(k_cut_glob<1>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
-  else if (a.size == 2u) hipLaunchKernelGGL(k_cut_glob<2>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
-  else hipLaunchKernelGGL(k_cut_glob<3>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
+  ko_by_size(a.size, [&](auto sz) { hipLaunchKernelGGL(k_cut_glob<decltype(sz)::value>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a); });
 }
 
 void launch_cut_count(const CutArgs &a, hipStream_t s) {

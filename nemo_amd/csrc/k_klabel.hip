@@ -2,7 +2,7 @@
 // name labels, on every listed graph in one call.  k_kl_tables turns the uploaded label sets into one label ->
 // mask table per chunk of 64 sets and a union filter of all named labels.  k_kl_lds is persistent: a workgroup
 // takes a contiguous block of work items (list position, chunk range), stages a graph's LDS image once
-// (ko_sweep.h) together with its hit list, the nodes whose label some set names, and then per chunk seeds the dead
+// (ko_sweep.h: the images of both tiers, the zeroing, the sweep, the lost word, the column sums) together with its hit list, the nodes whose label some set names, and then per chunk seeds the dead
 // words from the chunk's table, sweeps and writes one (lost, hit) word pair.  k_kl_glob is the same loop over the
 // CSR in device memory.  k_kl_count sums the words' bit columns over the list positions.
 #include "device.h"
@@ -90,18 +90,6 @@ __device__ __forceinline__ void kl_hits(const KlArgs &a, const GraphView &gv, co
   }
 }
 
-// The graph as the sweep reads it: k_kl_lds stages the LDS image (no barrier at the end), k_kl_glob points at the
-// CSR and keeps the dead words at the start of the workgroup's region.
-__device__ __forceinline__ KoImg<true> kl_image(std::true_type, const GraphView &gv, uint8_t *dyn, uint64_t *) {
-  return ko_stage_image(gv, dyn);
-}
-__device__ __forceinline__ KoImg<false> kl_image(std::false_type, const GraphView &gv, uint8_t *, uint64_t *reg) {
-  KoImg<false> g;
-  g.fp = gv.fp, g.fc = gv.fc, g.topo = gv.topo, g.lvl = gv.lvl, g.rule = nullptr, g.word = gv.word, g.dead = reg;
-  g.V = gv.V, g.L = gv.nlev;
-  return g;
-}
-
 // The workgroup's block of work items: item t is (list position a.pos[t / parts], chunk range t % parts).  A new
 // list position stages its graph and its hit list; every chunk of the range then zeroes the dead words, stores
 // the masks of the hits the chunk's table holds, sweeps and writes (lost, hit).  A chunk that hits nothing on the
@@ -111,7 +99,7 @@ __device__ __forceinline__ KoImg<false> kl_image(std::false_type, const GraphVie
 // labels in the same batched rounds and probes its table with each.
 template <bool LDS, bool LIST>
 __device__ __forceinline__ void kl_loop(const DevCorpus &c, const KlArgs &a, uint8_t *dyn) {
-  __shared__ uint64_t s_w[2][KO_BLOCK / 64];
+  __shared__ uint64_t s_w[2][KO_BLOCK / 64];  // the waves' hit words | ko_lost_word's
   __shared__ uint32_t s_nhit;
   const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
   uint64_t *reg = a.region + (uint64_t)blockIdx.x * a.region_words;
@@ -130,7 +118,7 @@ __device__ __forceinline__ void kl_loop(const DevCorpus &c, const KlArgs &a, uin
       pos = a.pos[ip];
       const GraphView gv = c.view(a.graph[pos]);
       if (tid == 0u) s_nhit = 0u;
-      g = kl_image(std::integral_constant<bool, LDS>{}, gv, dyn, reg);
+      g = ko_image(std::integral_constant<bool, LDS>{}, gv, dyn, reg);
       if (LDS) {
         const uint32_t image = knock::knock_lds_bytes(gv.V, gv.E, gv.nlev);
         head = reinterpret_cast<uint2 *>(dyn + image);
@@ -146,13 +134,9 @@ __device__ __forceinline__ void kl_loop(const DevCorpus &c, const KlArgs &a, uin
       }
     }
     uint64_t *dead = g.dead;
-    uint4 *z = reinterpret_cast<uint4 *>(dead);
-    const uint32_t pairs = (g.V + 1u) / 2u;
     const uint32_t c_lo = klabel::range_lo(a.n_chunks, a.parts, part), c_hi = klabel::range_lo(a.n_chunks, a.parts, part + 1u);
     for (uint32_t ci = c_lo; ci < c_hi; ci++) {
-      for (uint32_t i = tid; i < pairs; i += KO_BLOCK) z[i] = make_uint4(0u, 0u, 0u, 0u);
-      if (!LDS) __threadfence_block();
-      __syncthreads();
+      ko_zero_dead<LDS>(g);
       // seeds: a hit's node gets the mask of the chunk's sets that name its label (a node is one hit: plain stores)
       const uint64_t t0 = a.tab_off[ci], slots = a.tab_off[ci + 1u] - t0;
       uint64_t hw = 0ull;
@@ -196,17 +180,7 @@ __device__ __forceinline__ void kl_loop(const DevCorpus &c, const KlArgs &a, uin
       // barriers inside it, are taken by the whole workgroup or by none of it
       if (hit != 0ull) {
         ko_sweep<LDS>(g);
-        // lost: every root dead, per bit column (the level offsets are staged: read behind a barrier)
-        const uint32_t n_roots = g.L ? (uint32_t)g.lvl[1] : 0u;
-        uint64_t w = ~0ull;
-        for (uint32_t i = tid; i < n_roots; i += KO_BLOCK) w &= dead[g.topo[i]];
-#pragma unroll
-        for (int dd = 32; dd >= 1; dd >>= 1) w &= (uint64_t)__shfl_xor((unsigned long long)w, dd);
-        if (lane == 0u) s_w[1][wave] = w;
-        __syncthreads();
-        const uint32_t n = min(KO_CHUNK, a.n_sets - ci * KO_CHUNK);
-        lost = n_roots ? (s_w[1][0] & s_w[1][1] & s_w[1][2] & s_w[1][3]) : 0ull;
-        lost &= n == KO_CHUNK ? ~0ull : (1ull << n) - 1ull;
+        lost = ko_lost_word<LDS>(g, min(KO_CHUNK, a.n_sets - ci * KO_CHUNK), s_w[1]);  // every root dead, per bit column
       }
       if (tid == 0u)
         reinterpret_cast<uint4 *>(a.out)[(uint64_t)pos * a.n_chunks + ci] =
@@ -235,15 +209,8 @@ __global__ __launch_bounds__(KO_BLOCK) void k_kl_count(KlArgs a) {
   for (uint32_t base = 0; base < a.n; base += 64u) {
     const uint32_t i = base + lane;
     const uint4 x = i < a.n ? w[(uint64_t)i * a.n_chunks + ci] : make_uint4(0u, 0u, 0u, 0u);
-    const uint32_t sh = lane & 31u;
-    const bool up = lane >= 32u;
-#pragma unroll
-    for (int j = 0; j < 64; j++) {
-      const uint32_t l0 = __builtin_amdgcn_readlane(x.x, j), l1 = __builtin_amdgcn_readlane(x.y, j);
-      const uint32_t h0 = __builtin_amdgcn_readlane(x.z, j), h1 = __builtin_amdgcn_readlane(x.w, j);
-      nl += ((up ? l1 : l0) >> sh) & 1u;
-      nh += ((up ? h1 : h0) >> sh) & 1u;
-    }
+    nl += ko_colsum(x.x, x.y);
+    nh += ko_colsum(x.z, x.w);
   }
   a.cnt[(uint64_t)ci * 64u + lane] = nl;
   a.cnt[((uint64_t)a.n_chunks + ci) * 64u + lane] = nh;
@@ -255,26 +222,15 @@ void launch_kl_tables(const KlArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_kl_tables, dim3(std::min<uint32_t>((a.n_sets + per - 1u) / per, 4096u)), dim3(KO_BLOCK), 0, s, a);
 }
 
-uint32_t kl_lds_resident(uint32_t lds_bytes, uint32_t n_cu, bool list) {
-  int per_cu = 0;
-  const void *f = list ? (const void *)k_kl_lds<true> : (const void *)k_kl_lds<false>;
-  if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, KO_BLOCK, lds_bytes) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    return 0u;
-  }
-  return (uint32_t)per_cu * n_cu;
-}
+static const void *kl_lds_kernel(bool list) { return list ? (const void *)k_kl_lds<true> : (const void *)k_kl_lds<false>; }
+
+uint32_t kl_lds_resident(uint32_t lds_bytes, uint32_t n_cu, bool list) { return ko_lds_resident(kl_lds_kernel(list), lds_bytes, n_cu); }
 
 void launch_kl_lds(const DevCorpus &c, const KlArgs &a, uint32_t grid, hipStream_t s) {
   if (!a.n_tier || !a.n_chunks) return;
-  if (a.no_list) {
-    hipFuncSetAttribute((const void *)k_kl_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_total);
-    hipLaunchKernelGGL(k_kl_lds<false>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a);
-    return;
-  }
-  hipFuncSetAttribute((const void *)k_kl_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_total);
-  hipLaunchKernelGGL(k_kl_lds<true>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a);
+  hipFuncSetAttribute(kl_lds_kernel(!a.no_list), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_total);
+  if (a.no_list) hipLaunchKernelGGL(k_kl_lds<false>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a);
+  else hipLaunchKernelGGL(k_kl_lds<true>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a);
 }
 
 void launch_kl_glob(const DevCorpus &c, const KlArgs &a, uint32_t grid, hipStream_t s) {

@@ -121,7 +121,7 @@ void launch_ko_leaves(const DevCorpus &c, const KnockArgs &a, bool write, hipStr
   hipLaunchKernelGGL(k_ko_leaves, dim3(a.n_list), dim3(KO_BLOCK), 0, s, c, a, write ? 1u : 0u);
 }
 
-// ---- the sweep (KoImg, ko_stage_image and ko_sweep: ko_sweep.h) ------------------------------------
+// ---- the sweep (KoImg, the two tiers' images, ko_zero_dead and ko_sweep: ko_sweep.h) ----------------
 // lane b's return value: how many of the wave's 64 words have bit b set (a ballot per bit column)
 __device__ __forceinline__ uint32_t ko_colcount(uint64_t w) {
   if (__ballot(w != 0ull) == 0ull) return 0u;
@@ -202,13 +202,12 @@ __global__ __launch_bounds__(KO_BLOCK) void k_ko_lds(DevCorpus c, KnockArgs a) {
   const KoChunk k = ko_chunk(a, a.sel[blockIdx.x]);
   const GraphView gv = c.view(k.graph);
   const KoImg<true> g = ko_stage_image(gv, dyn);
-  uint4 *z = reinterpret_cast<uint4 *>(g.dead);
-  const uint32_t pairs = (gv.V + 1u) / 2u;
-  for (uint32_t i = tid; i < pairs; i += KO_BLOCK) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  __syncthreads();
+  ko_zero_dead<true>(g);  // its barrier ends the staging
   ko_run<true>(a, k, g);
   if (a.masks) {  // the V words out in 16-byte stores (ko_run ends behind a barrier)
+    const uint4 *z = reinterpret_cast<const uint4 *>(g.dead);
     uint4 *o = reinterpret_cast<uint4 *>(a.dead + k.moff);
+    const uint32_t pairs = (gv.V + 1u) / 2u;
     for (uint32_t i = tid; i < pairs; i += KO_BLOCK) o[i] = z[i];
   }
 }
@@ -216,18 +215,9 @@ __global__ __launch_bounds__(KO_BLOCK) void k_ko_lds(DevCorpus c, KnockArgs a) {
 // blockIdx.x = a chunk of the global tier: the same sweep over the CSR in device memory, the dead words in the
 // chunk's own region of a.dead (which is also its mask).  Correct, not tuned.
 __global__ __launch_bounds__(KO_BLOCK) void k_ko_glob(DevCorpus c, KnockArgs a) {
-  const uint32_t tid = threadIdx.x;
   const KoChunk k = ko_chunk(a, a.sel[blockIdx.x]);
-  const GraphView gv = c.view(k.graph);
-  uint64_t *dead = a.dead + k.moff;
-  uint4 *z = reinterpret_cast<uint4 *>(dead);
-  const uint32_t pairs = (gv.V + 1u) / 2u;
-  for (uint32_t i = tid; i < pairs; i += KO_BLOCK) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  __threadfence_block();
-  __syncthreads();
-  KoImg<false> g;
-  g.fp = gv.fp, g.fc = gv.fc, g.topo = gv.topo, g.lvl = gv.lvl, g.rule = nullptr, g.word = gv.word, g.dead = dead;
-  g.V = gv.V, g.L = gv.nlev;
+  const KoImg<false> g = ko_glob_image(c.view(k.graph), a.dead + k.moff);  // pointers only: nothing to order with the zeroing
+  ko_zero_dead<false>(g);
   ko_run<false>(a, k, g);
 }
 

@@ -3,7 +3,8 @@
 // a round's hypotheses are the sets of 1, 2 or 3 live candidate positions in colex rank order (cut_host.h), so
 // nothing but the candidate labels is uploaded; the work items are (list position, chunk range) in contiguous
 // blocks per workgroup (klabel_host.h).  k_lc_table hashes the candidates into one label -> position table.
-// k_lc_lds is persistent: on a new list position it stages the graph's LDS image (ko_sweep.h) and groups the
+// k_lc_lds is persistent: on a new list position it stages the graph's LDS image (ko_sweep.h, which also holds the
+// global tier's image, the zeroing, the sweep, the lost word and the column sums) and groups the
 // graph's hit nodes by live position; per chunk a lane unranks its set, ORs its bit into the nodes of its 1 to 3
 // rows, the workgroup sweeps and writes one lost word.  k_lc_glob is the same loop over the CSR in device memory.
 // k_lc_reduce counts a chunk's bit columns over the list positions against q (round 3: and clears the triples that
@@ -25,16 +26,6 @@ __global__ __launch_bounds__(KO_BLOCK) void k_lc_table(LcArgs a) {
   uint64_t h = klabel::first_slot(label, a.slots);
   while (atomicCAS(&a.key[h], 0u, label + 1u) != 0u) h = klabel::next_slot(h, a.slots);
   a.val[h] = p;
-}
-
-__device__ __forceinline__ KoImg<true> lc_image(std::true_type, const GraphView &gv, uint8_t *dyn, uint64_t *) {
-  return ko_stage_image(gv, dyn);
-}
-__device__ __forceinline__ KoImg<false> lc_image(std::false_type, const GraphView &gv, uint8_t *, uint64_t *reg) {
-  KoImg<false> g;
-  g.fp = gv.fp, g.fc = gv.fc, g.topo = gv.topo, g.lvl = gv.lvl, g.rule = nullptr, g.word = gv.word, g.dead = reg;
-  g.V = gv.V, g.L = gv.nlev;
-  return g;
 }
 
 // A graph's hit list, u32 entries: [0 .. k1] the rows' offsets, then the rows' nodes.  The first `cap` entries
@@ -91,7 +82,7 @@ __device__ __forceinline__ void lc_loop(const DevCorpus &c, const LcArgs &a, uin
       cur = ip;
       pos = a.pos[ip];
       const GraphView gv = c.view(a.graph[pos]);
-      g = lc_image(std::integral_constant<bool, LDS>{}, gv, dyn, reg);
+      g = ko_image(std::integral_constant<bool, LDS>{}, gv, dyn, reg);
       if (LDS) {
         const uint32_t image = knock::knock_lds_bytes(gv.V, gv.E, gv.nlev);
         ls.head = reinterpret_cast<uint32_t *>(dyn + image);
@@ -131,13 +122,9 @@ __device__ __forceinline__ void lc_loop(const DevCorpus &c, const LcArgs &a, uin
       __syncthreads();  // row p is now entries [p ? off[p - 1] : 0, off[p]) behind the offsets
     }
     uint64_t *dead = g.dead;
-    uint4 *z = reinterpret_cast<uint4 *>(dead);
-    const uint32_t pairs = (g.V + 1u) / 2u;
     const uint32_t c_lo = klabel::range_lo(a.n_chunks, a.parts, part), c_hi = klabel::range_lo(a.n_chunks, a.parts, part + 1u);
     for (uint32_t ci = c_lo; ci < c_hi; ci++) {
-      for (uint32_t i = tid; i < pairs; i += KO_BLOCK) z[i] = make_uint4(0u, 0u, 0u, 0u);
-      if (!LDS) __threadfence_block();
-      __syncthreads();
+      ko_zero_dead<LDS>(g);
       const uint32_t first = ci * KO_CHUNK, n = min(KO_CHUNK, a.n_hyp - first);
       // seeds: lane t's hypothesis is the set of rank first + t; it ORs its bit into the nodes of its rows
       if (wave == 0u) {
@@ -166,16 +153,7 @@ __device__ __forceinline__ void lc_loop(const DevCorpus &c, const LcArgs &a, uin
       // none of it
       if (hit != 0ull) {
         ko_sweep<LDS>(g);
-        // lost: every root dead, per bit column (the level offsets are staged: read behind a barrier)
-        const uint32_t n_roots = g.L ? (uint32_t)g.lvl[1] : 0u;
-        uint64_t w = ~0ull;
-        for (uint32_t i = tid; i < n_roots; i += KO_BLOCK) w &= dead[g.topo[i]];
-#pragma unroll
-        for (int dd = 32; dd >= 1; dd >>= 1) w &= (uint64_t)__shfl_xor((unsigned long long)w, dd);
-        if (lane == 0u) s_w[wave] = w;
-        __syncthreads();
-        lost = n_roots ? (s_w[0] & s_w[1] & s_w[2] & s_w[3]) : 0ull;
-        lost &= n == KO_CHUNK ? ~0ull : (1ull << n) - 1ull;
+        lost = ko_lost_word<LDS>(g, n, s_w);  // every root dead, per bit column
       }
       if (tid == 0u) {
         a.lost[(uint64_t)pos * a.n_chunks + ci] = lost;
@@ -208,18 +186,11 @@ __global__ __launch_bounds__(KO_BLOCK) void k_lc_reduce(LcArgs a) {
   if (ci >= a.n_chunks) return;
   uint32_t cnt = 0;
   uint64_t anyhit = 0ull;
-  const uint32_t sh = lane & 31u;
-  const bool up = lane >= 32u;
   for (uint32_t base = 0; base < a.n; base += 64u) {
     const uint32_t i = base + lane;
     const uint64_t x = i < a.n ? a.lost[(uint64_t)i * a.n_chunks + ci] : 0ull;
     if (SIZE == 1u && i < a.n) anyhit |= a.hit[(uint64_t)i * a.n_chunks + ci];
-    const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32);
-#pragma unroll
-    for (int j = 0; j < 64; j++) {
-      const uint32_t l0 = __builtin_amdgcn_readlane(x0, j), l1 = __builtin_amdgcn_readlane(x1, j);
-      cnt += ((up ? l1 : l0) >> sh) & 1u;
-    }
+    cnt += ko_colsum((uint32_t)x, (uint32_t)(x >> 32));
   }
   uint64_t cut = __ballot(cnt >= a.q);
   if (SIZE == 1u) {
@@ -227,14 +198,8 @@ __global__ __launch_bounds__(KO_BLOCK) void k_lc_reduce(LcArgs a) {
     for (int dd = 32; dd >= 1; dd >>= 1) anyhit |= (uint64_t)__shfl_xor((unsigned long long)anyhit, dd);
   }
   if (SIZE == 3u) {
-    bool sub = false;
     const uint64_t h = (uint64_t)ci * KO_CHUNK + lane;
-    if (h < a.n_hyp) {
-      const cuts::Pos p = cuts::unrank<3>(h);
-      const uint64_t r0 = cuts::rank2(p.a, p.b), r1 = cuts::rank2(p.a, p.c), r2 = cuts::rank2(p.b, p.c);
-      const uint64_t w0 = a.pairs[r0 >> 6], w1 = a.pairs[r1 >> 6], w2 = a.pairs[r2 >> 6];
-      sub = (((w0 >> (r0 & 63u)) | (w1 >> (r1 & 63u)) | (w2 >> (r2 & 63u))) & 1ull) != 0ull;
-    }
+    const bool sub = h < a.n_hyp && cuts::has_cut_pair(a.pairs, cuts::unrank<3>(h));
     cut &= ~__ballot(sub);
   }
   if (lane == 0u) {
@@ -273,41 +238,28 @@ void launch_lc_table(const LcArgs &a, hipStream_t s) {
 }
 
 static const void *lc_lds_kernel(uint32_t size) {
-  return size == 1u ? (const void *)k_lc_lds<1> : size == 2u ? (const void *)k_lc_lds<2> : (const void *)k_lc_lds<3>;
+  const void *f = nullptr;
+  ko_by_size(size, [&](auto sz) { f = (const void *)k_lc_lds<decltype(sz)::value>; });
+  return f;
 }
 
-uint32_t lc_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu) {
-  int per_cu = 0;
-  const void *f = lc_lds_kernel(size);
-  if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, KO_BLOCK, lds_bytes) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    return 0u;
-  }
-  return (uint32_t)per_cu * n_cu;
-}
+uint32_t lc_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu) { return ko_lds_resident(lc_lds_kernel(size), lds_bytes, n_cu); }
 
 void launch_lc_lds(const DevCorpus &c, const LcArgs &a, uint32_t grid, hipStream_t s) {
   if (!a.n_tier || !a.n_chunks) return;
   hipFuncSetAttribute(lc_lds_kernel(a.size), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_total);
-  if (a.size == 1u) hipLaunchKernelGGL(k_lc_lds<1>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a);
-  else if (a.size == 2u) hipLaunchKernelGGL(k_lc_lds<2>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a);
-  else hipLaunchKernelGGL(k_lc_lds<3>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a);
+  ko_by_size(a.size, [&](auto sz) { hipLaunchKernelGGL(k_lc_lds<decltype(sz)::value>, dim3(grid), dim3(KO_BLOCK), a.lds_total, s, c, a); });
 }
 
 void launch_lc_glob(const DevCorpus &c, const LcArgs &a, uint32_t grid, hipStream_t s) {
   if (!a.n_tier || !a.n_chunks) return;
-  if (a.size == 1u) hipLaunchKernelGGL(k_lc_glob<1>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
-  else if (a.size == 2u) hipLaunchKernelGGL(k_lc_glob<2>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
-  else hipLaunchKernelGGL(k_lc_glob<3>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a);
+  ko_by_size(a.size, [&](auto sz) { hipLaunchKernelGGL(k_lc_glob<decltype(sz)::value>, dim3(grid), dim3(KO_BLOCK), 0, s, c, a); });
 }
 
 void launch_lc_reduce(const LcArgs &a, hipStream_t s) {
   if (!a.n_chunks) return;
   const dim3 grid((a.n_chunks + KO_BLOCK / 64 - 1u) / (KO_BLOCK / 64));
-  if (a.size == 1u) hipLaunchKernelGGL(k_lc_reduce<1>, grid, dim3(KO_BLOCK), 0, s, a);
-  else if (a.size == 2u) hipLaunchKernelGGL(k_lc_reduce<2>, grid, dim3(KO_BLOCK), 0, s, a);
-  else hipLaunchKernelGGL(k_lc_reduce<3>, grid, dim3(KO_BLOCK), 0, s, a);
+  ko_by_size(a.size, [&](auto sz) { hipLaunchKernelGGL(k_lc_reduce<decltype(sz)::value>, grid, dim3(KO_BLOCK), 0, s, a); });
 }
 
 void launch_lc_support(const LcArgs &a, hipStream_t s) {

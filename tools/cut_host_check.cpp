@@ -1,7 +1,7 @@
 // cut_host_check — drives the host side of nemo_min_cuts (nemo_amd/csrc/cut_host.h): unrank(rank(x)) == x for
 // every pair and triple of up to 200 positions, ranks monotone and dense in colex order, the ranks around
 // 2^32 - 2 (2,953 live candidates give 4,287,437,076 triples, which just fits; 2,955 do not), the per-round limit
-// from both sides, every outcome of the candidate validation, the live list and the chunk and grid counts.
+// from both sides, round 3's cut-pair test against brute force for every triple of 9 positions, every outcome of the candidate validation, the live list and the chunk and grid counts.
 // Meant for the host sanitizers; it calls nothing on a device:
 //   g++ -std=c++17 -g -Wall -fsanitize=address,undefined -static-libasan -static-libubsan
 //       tools/cut_host_check.cpp -o tools/cut_host_check
@@ -98,6 +98,46 @@ static void check_large() {
   CHECK(a == 0 && b == 1 && c == 2);
 }
 
+// has_cut_pair against a brute-force membership test: every triple of K = 9 positions, under no cut pair, every
+// single one of the 36, a few mixed sets and all of them; then a pair whose rank lies in the second word
+static void check_cut_pair() {
+  const uint32_t K = 9;
+  const uint64_t n2 = cuts::choose2(K);
+  bool cut[K][K];
+  auto run = [&](const std::vector<uint64_t> &ranks) {
+    uint64_t words[2] = {0, 0};  // K = 9's 36 pairs lie in the first
+    for (uint32_t y = 0; y < K; y++)
+      for (uint32_t x = 0; x < K; x++) cut[x][y] = false;
+    for (uint64_t r : ranks) {
+      uint32_t x, y;
+      cuts::unrank2(r, &x, &y);
+      cut[x][y] = true;
+      words[r >> 6] |= 1ull << (r & 63u);
+    }
+    for (uint32_t c = 2; c < K; c++)
+      for (uint32_t b = 1; b < c; b++)
+        for (uint32_t a = 0; a < b; a++) {
+          const cuts::Pos p = cuts::unrank<3>(cuts::rank3(a, b, c));
+          CHECK(p.a == a && p.b == b && p.c == c);
+          CHECK(cuts::has_cut_pair(words, p) == (cut[a][b] || cut[a][c] || cut[b][c]));
+        }
+  };
+  run({});
+  for (uint64_t r = 0; r < n2; r++) run({r});
+  run({0, 7, 35});
+  run({3, 4, 5, 20, 21, 34});
+  std::vector<uint64_t> all;
+  for (uint64_t r = 0; r < n2; r++) all.push_back(r);
+  run(all);
+  // positions past 11 have pair ranks past 64: the second word.  Triples of {0, 1, 12, 13} with the pair (12, 13) a cut
+  uint64_t words[2] = {0, 0};
+  const uint64_t r = cuts::rank2(12, 13);
+  CHECK(r >= 64 && r < 128);
+  words[r >> 6] |= 1ull << (r & 63u);
+  CHECK(cuts::has_cut_pair(words, cuts::Pos{0, 12, 13}) && cuts::has_cut_pair(words, cuts::Pos{1, 12, 13}));
+  CHECK(!cuts::has_cut_pair(words, cuts::Pos{0, 1, 12}) && !cuts::has_cut_pair(words, cuts::Pos{0, 1, 13}));
+}
+
 static void check_cands() {
   size_t where = 99;
   CHECK(cuts::check_cands(nullptr, 0, 10, &where) == cuts::CAND_OK);
@@ -136,6 +176,7 @@ static void check_live_and_grid() {
 int main() {
   check_small();
   check_large();
+  check_cut_pair();
   check_cands();
   check_live_and_grid();
   printf("cut_host_check OK\n");
