@@ -1,43 +1,14 @@
 // k_diff.hip — differential provenance (differential-provenance.go:18-146),
 // edge pulls (pre-post-prov.go:288-459, Q24) and the run-0 trigger patterns of
 // corrections.go:30-34,121-125 / extensions.go:63-67.
+// The node bits, the LDS image and the level walk of k_diff_lds are diff_walk.h's,
+// shared with k_sdiff.hip; the windowed k_diff keeps its own sweep (diff_window_sweep).
 #include "device.h"
+#include "diff_walk.h"
 #include "internal.h"
 
 namespace nemo {
 
-#define DB_F 0x01u
-#define DB_B 0x02u
-#define DB_PRESENT 0x04u
-#define DB_LEAF 0x08u
-#define DB_D 0x10u
-#define DB_LP 0x20u
-
-// LDS image of run 0's post graph for k_diff_lds: u16 rows both ways, a rule
-// bitmap and the entry's node bits (~5V + 4E bytes, three workgroups per CU
-// at the tier caps, so a few hundred diff entries run in one round); the Kahn
-// order (coalesced, one load per level) and the depths stay in HBM.
-struct DiffLds {
-  uint16_t *rp, *fp, *rc, *fc;
-  uint32_t *rule;
-  uint8_t *bits;
-};
-__device__ __forceinline__ DiffLds diff_carve(void *base, uint32_t V, uint32_t E, uint32_t L) {
-  uint8_t *p = (uint8_t *)base;
-  DiffLds d;
-  d.rp = (uint16_t *)p;
-  p += lds_align(2u * (V + 1u));
-  d.fp = (uint16_t *)p;
-  p += lds_align(2u * (V + 1u));
-  d.rc = (uint16_t *)p;
-  p += lds_align(2u * E);
-  d.fc = (uint16_t *)p;
-  p += lds_align(2u * E);
-  d.rule = (uint32_t *)p;
-  p += lds_align(4u * ((V + 31u) / 32u));
-  d.bits = p;
-  return d;
-}
 __device__ __forceinline__ bool diff_lds_fits(const DevCorpus &c, const GraphView &gv) {
   return tier_fits(c.t_diff, gv.V, gv.E, gv.nlev);
 }
@@ -475,20 +446,19 @@ __global__ __launch_bounds__(B) void k_diff(DevCorpus c, DiffArgs a) {
 #undef DK_T
 }
 
-// k_diff over the LDS graph tier: the same three level sweeps (Fwd*, Bwd*,
-// depth) with run 0's post graph rows and the entry's node bits in LDS, so
-// the dependent parent/child probes of a level are LDS round trips.
+// k_diff over the LDS graph tier: run 0's post graph rows and the entry's node
+// bits in LDS (three workgroups per CU at the tier caps, so a few hundred diff
+// entries run in one round), so the dependent parent/child probes of a level
+// are LDS round trips.  Stages the image, builds the rule bitmap, seeds the
+// present goals; the sweeps and the tail are diff_walk's (diff_walk.h).
 __global__ __launch_bounds__(NEMO_BLOCK) void k_diff_lds(DevCorpus c, DiffArgs a) {
   extern __shared__ __align__(16) uint8_t dyn[];
-  __shared__ int32_t s_max;
   const uint32_t e = blockIdx.x, tid = threadIdx.x;
   const GraphView gv = c.view(a.g0);
   if (!diff_lds_fits(c, gv)) return;  // k_diff's graph
   const LabelSrc src = diff_label_src(c, a, e);
-  const uint32_t V = gv.V, nl = gv.nlev;
-  DiffLds L = diff_carve(dyn, V, gv.E, nl);
-  uint8_t *mask = a.mask + (size_t)e * V;
-  int32_t *depth = a.depth + (size_t)e * V;  // HBM: only D nodes touch it
+  const uint32_t V = gv.V;
+  DiffLds L = diff_carve(dyn, V, gv.E);
   {
     const StageDesc d[4] = {{gv.rp, L.rp, V + 1, ST_U16}, {gv.fp, L.fp, V + 1, ST_U16},
                             {gv.rc, L.rc, gv.E, ST_U16},  {gv.fc, L.fc, gv.E, ST_U16}};
@@ -496,7 +466,6 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_diff_lds(DevCorpus c, DiffArgs a
   }
   for (uint32_t w = tid; w < (V + 31) / 32; w += NEMO_BLOCK) L.rule[w] = 0;
   for (uint32_t v = tid; v < V; v += NEMO_BLOCK) L.bits[v] = 0;
-  if (tid == 0) s_max = -1;
   __syncthreads();
   for (uint32_t base = 0; base < V; base += NEMO_BLOCK) {
     const uint32_t v = base + tid;
@@ -506,77 +475,10 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_diff_lds(DevCorpus c, DiffArgs a
       if (b) atomicOr(&L.rule[v >> 5], b);
     }
   }
-  uint8_t *bits = L.bits;
-  diff_fail_goals(a, src, bits, a.r0idx);
-  __syncthreads();
-#define LRULE(v) ((L.rule[(v) >> 5] >> ((v) & 31)) & 1u)
-#define GOOD(v) (!LRULE(v) && !(bits[v] & DB_PRESENT))
-  for (uint32_t l = 0; l < nl; l++) {
-    for (uint32_t i = gv.lvl[l] + tid; i < gv.lvl[l + 1]; i += NEMO_BLOCK) {
-      const uint32_t v = gv.topo[i];
-      bool fw = GOOD(v);
-      for (uint32_t j = L.rp[v]; j < L.rp[v + 1] && !fw; j++) fw = (bits[L.rc[j]] & DB_F) != 0;
-      if (fw) bits[v] |= DB_F;
-    }
-    __syncthreads();
-  }
-  for (uint32_t l = nl; l-- > 0;) {
-    for (uint32_t i = gv.lvl[l] + tid; i < gv.lvl[l + 1]; i += NEMO_BLOCK) {
-      const uint32_t v = gv.topo[i];
-      bool bw = GOOD(v);
-      for (uint32_t j = L.fp[v]; j < L.fp[v + 1] && !bw; j++) bw = (bits[L.fc[j]] & DB_B) != 0;
-      uint8_t b = bits[v];
-      if (bw) b |= DB_B;
-      if ((b & DB_F) && bw) b |= DB_D;
-      bits[v] = b;
-    }
-    __syncthreads();
-  }
-#undef GOOD
-  // longest path from a D root (Kahn-level DP restricted to D)
-  for (uint32_t l = 0; l < nl; l++) {
-    for (uint32_t i = gv.lvl[l] + tid; i < gv.lvl[l + 1]; i += NEMO_BLOCK) {
-      const uint32_t v = gv.topo[i];
-      const uint8_t b = bits[v];
-      if (!(b & DB_D)) continue;
-      uint32_t d = 0;
-      for (uint32_t j = L.rp[v]; j < L.rp[v + 1]; j++) {
-        const uint32_t p = L.rc[j];
-        if (bits[p] & DB_D) d = max(d, (uint32_t)depth[p] + 1u);
-      }
-      depth[v] = (int32_t)d;
-      if (!LRULE(v)) {
-        bool leaf = true;
-        for (uint32_t j = L.fp[v]; j < L.fp[v + 1]; j++)
-          if (bits[L.fc[j]] & DB_D) leaf = false;
-        if (leaf) bits[v] = b | DB_LEAF;
-      }
-    }
-    __syncthreads();
-  }
-  for (uint32_t v = tid; v < V; v += NEMO_BLOCK) mask[v] = (bits[v] & DB_D) ? 1 : 0;
-  for (uint32_t r = tid; r < V; r += NEMO_BLOCK) {
-    if (!(bits[r] & DB_D) || !LRULE(r)) continue;
-    bool lp = false;
-    for (uint32_t j = L.fp[r]; j < L.fp[r + 1]; j++) {
-      const uint32_t x = L.fc[j];
-      if ((bits[x] & (DB_D | DB_LEAF)) == (DB_D | DB_LEAF)) lp = true;
-    }
-    if (lp) {
-      bits[r] |= DB_LP;
-      atomicMax(&s_max, depth[r] + 1);
-    }
-  }
-  __syncthreads();
-  const int32_t mx = s_max;
-  for (uint32_t r = tid; r < V; r += NEMO_BLOCK) {
-    if ((bits[r] & DB_LP) && depth[r] + 1 == mx) {
-      const uint32_t k = atomicAdd(a.n_missing, 1u);
-      a.missing[2 * k] = e;
-      a.missing[2 * k + 1] = r;
-    }
-  }
-#undef LRULE
+  diff_fail_goals(a, src, L.bits, a.r0idx);
+  // depths in HBM: only D nodes touch them
+  diff_walk<NEMO_BLOCK, WF_NONE, false>(gv, L, L.bits, a.depth + (size_t)e * V,
+                                        DiffOut{a.mask + (size_t)e * V, a.missing, a.n_missing, e});
 }
 
 // ---- edge pulls: which 0 = raw, 1 = simplified (graph'), 2 = diff entry ---------
