@@ -990,6 +990,68 @@ func (n *Neo4J) MinLabelCuts(iters []uint, cond string, candLabels []uint32, max
 	return res, stats, nil
 }
 
+// GroupCut is one minimal cut over fault events: a smallest set of candidate
+// groups whose joint loss defeats the outcome on at least the asked number of
+// listed runs.
+type GroupCut struct {
+	Groups []uint32 // positions in the group list, ascending
+	NLost  uint32   // the listed runs it breaks (a run listed twice counts twice)
+}
+
+// MinGroupCuts is MinLabelCuts with groups of labels as candidates
+// (nemo_min_group_cuts): a fault event that removes many clock goals at once,
+// such as the crash of a node, is one candidate, so "one crash plus one
+// omission" is a pair.  Among the groups it returns every minimal set of at
+// most maxSize (1..3) candidates whose loss together defeats the outcome on at
+// least minRuns of the listed runs' pre or post provenance (0: on every one of
+// them).  Minimality is over the positions in the group list.  The cuts come
+// sorted by size, then by the colex rank of their positions in the list of live
+// candidates.  The second result holds, per size 1..3, the live candidates
+// entering the round, the hypotheses evaluated and the minimal cuts found.
+func (n *Neo4J) MinGroupCuts(iters []uint, cond string, groups [][]uint32, maxSize uint, minRuns uint, sinksOnly bool) ([]*GroupCut, [9]uint64, error) {
+	var stats [9]uint64
+	its := make([]C.uint32_t, len(iters)+1)
+	for i, it := range iters {
+		its[i] = C.uint32_t(it)
+	}
+	off := make([]C.uint64_t, len(groups)+1)
+	var labels []C.uint32_t
+	for k, group := range groups {
+		for _, l := range group {
+			labels = append(labels, C.uint32_t(l))
+		}
+		off[k+1] = C.uint64_t(len(labels))
+	}
+	labels = append(labels, 0) // never empty: &labels[0] below
+	var flags C.uint32_t
+	if sinksOnly {
+		flags = C.NEMO_KL_SINKS
+	}
+	if err := n.err(C.nemo_min_group_cuts(n.ctx, &its[0], C.size_t(len(iters)), condIndex(cond), &off[0], &labels[0], C.size_t(len(groups)), C.uint32_t(maxSize), C.uint32_t(minRuns), flags)); err != nil {
+		return nil, stats, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_min_group_cuts(n.ctx, nil, nil, 0, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	rows, nLost := make([]C.nemo_group_cut, cnt+1), make([]C.uint32_t, cnt+1)
+	if err := n.err(C.nemo_fetch_min_group_cuts(n.ctx, &rows[0], &nLost[0], cnt, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	if err := n.err(C.nemo_fetch_min_group_cut_stats(n.ctx, (*C.uint64_t)(unsafe.Pointer(&stats[0])))); err != nil {
+		return nil, stats, err
+	}
+	res := make([]*GroupCut, cnt)
+	for k, gc := range rows[:cnt] {
+		m := &GroupCut{NLost: uint32(nLost[k])}
+		for j := 0; j < int(gc.size); j++ {
+			m.Groups = append(m.Groups, uint32(gc.group[j]))
+		}
+		res[k] = m
+	}
+	return res, stats, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

@@ -245,8 +245,8 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       in LDS; graphs past it, and graphs of 65536 nodes or more, run
  *                       the sweep over the CSR in device memory (default and upper
  *                       bound 81920; 0 = every graph in device memory); nemo_min_cuts,
- *                       nemo_knockout_labels and nemo_min_label_cuts take their tier
- *                       from the same option
+ *                       nemo_knockout_labels, nemo_min_label_cuts and
+ *                       nemo_min_group_cuts take their tier from the same option
  *   "cut_grid"          most workgroups of nemo_min_cuts' persistent sweeps (0, default:
  *                       as many as are resident on the device, at most one per chunk
  *                       of 64 hypotheses); a test knob: 1 makes one workgroup take
@@ -256,7 +256,8 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       "cut_grid", a test knob: 1 makes one workgroup walk every
  *                       listed graph in turn, small values split a graph's chunks
  *                       into few ranges; the tier is "knock_lds_max"'s;
- *                       nemo_min_label_cuts' sweeps take the same cap
+ *                       nemo_min_label_cuts' and nemo_min_group_cuts' sweeps take the
+ *                       same cap
  *   "kl_hitlist"        1 (default, also -1): the LDS-tier sweep of nemo_knockout_labels
  *                       lists, once per graph, the nodes whose label some set names,
  *                       and a chunk of 64 sets probes its table with those alone.  0:
@@ -704,6 +705,83 @@ int nemo_fetch_min_label_cuts(nemo_ctx *ctx, nemo_label_cut *out, uint32_t *n_lo
 /* As nemo_fetch_min_cut_stats: per size s = 1..3, out[3 (s - 1) ..]: live
  * candidates entering the round, hypotheses evaluated, minimal cuts found.     */
 int nemo_fetch_min_label_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
+
+/* ---- minimal cut sets over fault events: groups of labels as candidates ----
+ * nemo_min_label_cuts with candidates that are sets of labels: a fault event
+ * that removes many labels at once (a crash removes every clock goal its node
+ * would send or receive from then on) is one candidate, and a hypothesis of one
+ * crash and one omission is a pair.  The subject (a raw loaded graph),
+ * dead_F(v), the roots and "the outcome is lost under F"
+ * (roots_dead == n_roots > 0) are the knock-out definitions above.
+ * Candidates and removal sets: candidate k is the label set
+ * G_k = group_labels[group_off[k] .. group_off[k+1]).  For a set S of candidate
+ * positions, F(i,S) is every node of graph g = 2 * run_index(iters[i]) + cond,
+ * goal or rule, whose label lies in the union of G_k for k in S.  Under
+ * NEMO_KL_SINKS only sink goals are in F(i,S).  flags is 0 or NEMO_KL_SINKS.
+ * Cuts: lost_count(S) is the number of list positions i on which the outcome is
+ * lost under F(i,S); a run listed twice counts twice.  q = min_runs, where 0
+ * means n; min_runs > n is NEMO_ERR_INVALID.  S is a cut iff n > 0 and
+ * lost_count(S) >= q.  A listed graph without roots is never lost.  F is
+ * monotone in S, so lost and lost_count are, and every superset of a cut is a
+ * cut; S is minimal iff no proper subset of its candidates is a cut.
+ * Minimality is over candidate positions, not over label sets: two candidates
+ * with equal or nested groups are different candidates, and if each is a cut
+ * alone, each is a row.  A pair of nested groups is never a minimal cut; that
+ * follows from monotonicity and needs no special handling: the pair removes
+ * what the larger group removes alone, so the pair is a cut only if the larger
+ * candidate is one alone, and then it was no live candidate of round 2.
+ * Legal input: an empty group is legal, it hits nothing and is never live; a
+ * label named twice in a group counts once; a label that no listed node
+ * carries matches nothing.
+ * Rounds: nemo_min_label_cuts' rounds over candidate positions.  Round 1
+ * evaluates the K = n_groups singletons on every list position and keeps the
+ * lost bit and the hit bit.  The live list holds, in candidate order, the
+ * candidates that are no cut alone and whose group hit at least one listed
+ * graph, K1 entries (S and S without a candidate that hits no listed node
+ * remove the same nodes).  Round 2 evaluates all C(K1,2) pairs of live
+ * positions; every pair with lost_count >= q is minimal.  Round 3 evaluates all
+ * C(K1,3) triples; a triple with lost_count >= q is minimal iff none of its
+ * three pairs was a cut in round 2.  max_size must be 1, 2 or 3.
+ * Hypothesis index: the colex rank of nemo_min_cuts over the live positions
+ * (a < b < c: C(c,3) + C(b,2) + a, pairs C(b,2) + a, singles a).  The rows are
+ * sorted by (size, rank); a row's entries are candidate positions (indices into
+ * the group list), ascending, unused entries UINT32_MAX; n_lost[k] is
+ * lost_count of row k.
+ * NEMO_ERR_INVALID, all checked on the host before anything is uploaded: a
+ * decreasing group_off (the message gives the group); a label equal to
+ * UINT32_MAX, which is no label (the message gives the group and the position
+ * in group_labels); group_off == NULL with n_groups > 0 or group_labels == NULL
+ * where the groups name a label (there is no implicit event list); max_size
+ * outside 1..3 ("max_size must be 1, 2 or 3"); min_runs > n; cond outside
+ * 0 / 1; unknown flags.  NEMO_ERR_LIMIT: more than 2^32 - 1 labels named in all,
+ * or more than 2^24 labels in one group (both read from group_off alone,
+ * before any label is; split such a group); more distinct labels D than leave
+ * D + 1 + V <= 2^32 - 1 for the largest listed graph; a round of more than
+ * 2^32 - 2 hypotheses; a round with n * ceil(hyps / 64) > 2^28 words (shorten
+ * the group list or the run list).  The two round limits are checked per
+ * round, before that round's launch (K1 is known only after round 1), and the
+ * call then leaves no results.  An iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; a node context, and a call without a loaded corpus, return
+ * NEMO_ERR_STATE.
+ * n == 0 or n_groups == 0 gives zero rows and NEMO_OK.  The call blocks until
+ * the rows are on the host.  The results are the call's own state: valid until
+ * the next nemo_min_group_cuts or nemo_load_corpus (the fetches return
+ * NEMO_ERR_STATE otherwise), independent of the knock-out, cut, label knock-out,
+ * label cut, diff, symmetric diff, nearest and class state in both directions.
+ * No option of its own: the tier is "knock_lds_max"'s, the grid cap "kl_grid"'s. */
+typedef struct nemo_group_cut {
+  uint32_t size;     /* 1..3                                                         */
+  uint32_t group[3]; /* candidate positions (indices into the group list), ascending, unused = UINT32_MAX */
+} nemo_group_cut;
+int nemo_min_group_cuts(nemo_ctx *ctx, const uint32_t *iters, size_t n, int cond,
+                        const uint64_t *group_off /* [n_groups + 1] */, const uint32_t *group_labels,
+                        size_t n_groups, uint32_t max_size, uint32_t min_runs, uint32_t flags);
+/* out[k] for every minimal cut k, n_lost[k] its lost_count (n_lost may be NULL);
+ * out == NULL queries *n_out.                                                  */
+int nemo_fetch_min_group_cuts(nemo_ctx *ctx, nemo_group_cut *out, uint32_t *n_lost, uint64_t cap, uint64_t *n_out);
+/* As nemo_fetch_min_cut_stats: per size s = 1..3, out[3 (s - 1) ..]: live
+ * candidates entering the round, hypotheses evaluated, minimal cuts found.     */
+int nemo_fetch_min_group_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

@@ -1,17 +1,7 @@
 // api_lcuts.hip — nemo_min_label_cuts and its fetches (k_lcuts.hip, lcut_host.h; DESIGN.md §Minimal cut sets by label).
-// knock_api.h holds what it shares with api_klabel.hip (the level counts, the tier split, a round's dynamic LDS) and
-// with api_cuts.hip (the rounds' sizes and the rows).
+// knock_api.h holds what it shares with api_klabel.hip (the level counts, the tier split, a round's dynamic LDS), with
+// api_cuts.hip (the rounds' sizes and the rows) and with api_gcuts.hip (a round's limits, launch plan and driver).
 #include "knock_api.h"
-
-namespace {
-
-struct LcPlan {  // one round's launches
-  uint32_t lds_total = 0;
-  uint64_t rw_lds = 0, rw_glob = 0;  // region words of a workgroup
-  uint64_t r_lds = 1, r_glob = 1;    // most workgroups
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -59,20 +49,7 @@ int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, 
     if ((rc = run_index(c, iters[i], &r))) return rc;
     desc[i] = 2 * r + (uint32_t)cond;
   }
-  auto limit = [&](uint64_t k, uint32_t sz) -> int {
-    switch (lcuts::round_check(n, k, sz)) {
-      case lcuts::ROUND_HYPS:
-        return fail(c, NEMO_ERR_LIMIT,
-                    "nemo_min_label_cuts: the sets of %u of %llu live candidates exceed 2^32 - 2 hypotheses: shorten the candidate list or the run list",
-                    sz, (unsigned long long)k);
-      case lcuts::ROUND_WORDS:
-        return fail(c, NEMO_ERR_LIMIT,
-                    "nemo_min_label_cuts: %zu list positions x %llu chunks of 64 sets of %u exceed 2^28 words: shorten the candidate list or the run list",
-                    n, (unsigned long long)cuts::chunks(cuts::round_hyps(k, sz)), sz);
-      default:
-        return NEMO_OK;
-    }
-  };
+  auto limit = [&](uint64_t k, uint32_t sz) -> int { return label_round_limit(c, "nemo_min_label_cuts", "candidate list", n, k, sz); };
   if (n && K && (rc = limit(K, 1))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_whole(c))) return rc;  // may read any graph's build outputs
@@ -89,29 +66,11 @@ int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, 
   GroupTimer timer(c, "k_lcuts");
   // the tiers, the rounds' LDS and what a workgroup keeps in device memory
   const Tiers tr = split_tiers(c, desc, n);
-  const uint32_t n_lds = tr.n_lds, n_glob = tr.n_glob;
-  const uint64_t glob_v = tr.glob_v;
-  const uint32_t cap = c->opt.kl_grid;
-  LcPlan plan[3];
+  LabelPlan plan[3];  // K bounds every round's live positions
   uint64_t reg_need = 1;
-  for (uint32_t sz = 1; sz <= max_size; sz++) {  // K bounds every round's live positions
-    LcPlan &p = plan[sz - 1];
-    uint32_t res_lds = 1;
-    if (n_lds) {
-      if ((rc = ko_lds_total(c, "nemo_min_label_cuts", "k_lc_lds", [&](uint32_t b) { return nemo::lc_lds_resident(sz, b, cs.dc.n_cu); },
-                             tr.image, 4 * lcuts::list_entries(K, tr.lds_v), KO_LDS_STATIC, &p.lds_total, &res_lds)))
-        return rc;
-      for (size_t k = 0; k < n_lds; k++) {
-        const uint32_t g = desc[desc[n + k]];
-        p.rw_lds = std::max(p.rw_lds, lcuts::region_words(0, lcuts::list_entries(K, cs.nv(g)), (p.lds_total - tier_image(c, g)) / 4u));
-      }
-    }
-    p.rw_glob = lcuts::region_words(knock::dead_words(glob_v), lcuts::list_entries(K, glob_v), 0);
-    p.r_lds = klabel::region_grid(res_lds, p.rw_lds), p.r_glob = klabel::region_grid(2ull * cs.dc.n_cu, p.rw_glob);
-    if (cap) p.r_lds = std::min<uint64_t>(p.r_lds, cap), p.r_glob = std::min<uint64_t>(p.r_glob, cap);
-    if (n_lds) reg_need = std::max(reg_need, p.r_lds * p.rw_lds);
-    if (n_glob) reg_need = std::max(reg_need, p.r_glob * p.rw_glob);
-  }
+  if ((rc = label_plans(c, "nemo_min_label_cuts", "k_lc_lds", [&](uint32_t sz, uint32_t b) { return nemo::lc_lds_resident(sz, b, cs.dc.n_cu); },
+                        desc, n, tr, K, KO_LDS_STATIC, max_size, plan, &reg_need)))
+    return rc;
   const uint64_t ck1 = cuts::chunks(K), slots = lcuts::table_slots(K);
   {
     const uint64_t need[10] = {K, 2 * K, K, slots, slots, 2 * (uint64_t)n, (uint64_t)n * ck1, reg_need, 2 * ck1, (uint64_t)n * ck1};
@@ -139,42 +98,11 @@ int nemo_min_label_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int cond, 
     if ((rc = timed(c, "k_lc_table", b, 0, [&] { nemo::launch_lc_table(a[0], s); }))) return rc;
     bytes += b + 4.0 * (double)slots;
   }
-  // One round: the two tiers' sweeps, then the reduction.  The byte model: a work item reads its graph's image
-  // (4 E + 12 V + 4 L + 8) and its 4 V labels twice (count, scatter); a chunk writes 8 bytes (round 1: 16);
-  // ops = E child words per chunk, an upper bound (the host does not know which chunks hit nothing and skip the
-  // sweep); the global tier adds 16 V per chunk for its dead words in device memory.  The reduction reads every
-  // word once and writes one per chunk.
+  // one round: the two tiers' sweeps, then the reduction (knock_api.h; its byte model with nothing more per chunk)
   auto round = [&](nemo::LcArgs &r) -> int {
-    if (!r.n_chunks) return NEMO_OK;
-    const LcPlan &p = plan[r.size - 1];
-    const uint64_t ck = r.n_chunks;
-    const double per_word = r.size == 1 ? 16.0 : 8.0;
-    for (int tier = 0; tier < 2; tier++) {
-      const uint32_t nt = tier ? n_glob : n_lds;
-      if (!nt) continue;
-      const uint64_t res = tier ? p.r_glob : p.r_lds;
-      const klabel::Split sp = klabel::split(nt, ck, res);
-      const uint32_t grid = klabel::grid(sp.items, res, cap);
-      double b = 0, o = 0;
-      for (uint32_t k = 0; k < nt; k++) {
-        const uint32_t g = desc[desc[n + (tier ? n_lds : 0) + k]];
-        const double V = (double)cs.nv(g), E = (double)cs.ne(g), L = (double)cs.kl_nlev[g];
-        b += sp.parts * (4.0 * E + 12.0 * V + 4.0 * L + 8.0 + 8.0 * V) + (double)ck * (per_word + (tier ? 16.0 * V : 0.0));
-        o += (double)ck * E;
-      }
-      r.pos = cs.d_lcdesc.p + n + (tier ? n_lds : 0);
-      r.n_tier = nt, r.parts = sp.parts;
-      r.lds_total = tier ? 0u : p.lds_total;
-      r.region_words = tier ? p.rw_glob : p.rw_lds;
-      r.dead_words = tier ? knock::dead_words(glob_v) : 0;
-      if (tier) rc = timed(c, "k_lc_glob", b, o, [&] { nemo::launch_lc_glob(cs.dc, r, grid, s); });
-      else rc = timed(c, "k_lc_lds", b, o, [&] { nemo::launch_lc_lds(cs.dc, r, grid, s); });
-      if (rc) return rc;
-      bytes += b, ops += o;
-    }
-    const double b_red = per_word * (double)n * (double)ck + per_word * (double)ck;
-    bytes += b_red;
-    return timed(c, "k_lc_reduce", b_red, 0, [&] { nemo::launch_lc_reduce(r, s); });
+    return label_round(
+        c, plan[r.size - 1], tr, desc, r, cs.d_lcdesc.p, 0.0, "k_lc_lds", "k_lc_glob", [&](uint32_t grid) { nemo::launch_lc_lds(cs.dc, r, grid, s); },
+        [&](uint32_t grid) { nemo::launch_lc_glob(cs.dc, r, grid, s); }, &bytes, &ops);
   };
   // round 1: every candidate is live
   a[0].lmap = cs.d_lcmap.p, a[0].k1 = (uint32_t)K, a[0].n_hyp = (uint32_t)K, a[0].n_chunks = (uint32_t)ck1;

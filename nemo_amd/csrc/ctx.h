@@ -378,6 +378,33 @@ struct CorpusState : GraphSizes {
   DevBuf<uint32_t> d_lcscan;         // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
   DevBuf<uint32_t> d_lcrows;         // [rows][4] nemo_label_cut, then [rows] n_lost
 
+  // minimal cut sets over fault events (k_gcuts.hip): the call's own state, void after the next nemo_min_group_cuts or
+  // load; independent of knock-out, cut, label knock-out, label cut, diff, nearest and class state (kl_nlev above is
+  // the load's, not a result).  One group d_gc*, which grows only inside nemo_min_group_cuts, each buffer to the
+  // largest request so far, behind a wait for the stream: the first eleven together once the call is checked, in this
+  // order; d_gcw[1..2], d_gclost[1..2] and d_gcscan together once round 1 has left the live list; d_gcrows alone once
+  // the totals are known
+  bool gc_done = false;
+  uint64_t gc_rows = 0;              // rows of the last call (in nemo_ctx::h_gcuts: [rows][4], then [rows] n_lost)
+  uint64_t gc_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size: live candidates, hypotheses, minimal cuts
+  std::vector<uint32_t> gc_desc;     // the last call's uploads: [n] graphs | the LDS tier's list positions | the global tier's,
+  std::vector<uint32_t> gc_off;      // ... [K + 1] the groups' offsets from the first group's,
+  std::vector<uint32_t> gc_ident;    // ... [K] the identity (a row's entries are candidate positions),
+  std::vector<uint32_t> gc_live;     // ... [K1] live position -> candidate position
+  DevBuf<uint32_t> d_gcoff;          // [K + 1]
+  DevBuf<uint32_t> d_gcgrow;         // the groups' labels, rewritten as rows
+  DevBuf<uint32_t> d_gcident;        // [K]
+  DevBuf<uint32_t> d_gclive;         // [K]
+  DevBuf<uint32_t> d_gckey;          // the table's keys; then the rows handed out (one word)
+  DevBuf<uint32_t> d_gcval;          // ... and rows
+  DevBuf<uint32_t> d_gcdesc;         // [2 n]
+  DevBuf<uint64_t> d_gchit;          // [n][chunks] round 1's hit words
+  DevBuf<uint64_t> d_gcreg;          // the workgroups' regions: the hit list's rest, k_gc_glob's dead words
+  DevBuf<uint64_t> d_gcw[3];         // the rounds' cut words, one per chunk of 64 ranks (round 1: then the any-hit words)
+  DevBuf<uint64_t> d_gclost[3];      // the rounds' lost words [n][chunks]
+  DevBuf<uint32_t> d_gcscan;         // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
+  DevBuf<uint32_t> d_gcrows;         // [rows][4] nemo_group_cut, then [rows] n_lost
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -464,11 +491,12 @@ struct nemo_ctx {
   hipEvent_t ev_cuts = nullptr;    // nemo_min_cuts' counts / words / totals / rows have reached pinned memory
   hipEvent_t ev_klabel = nullptr;  // nemo_knockout_labels' level counts / words / counts have reached pinned memory
   hipEvent_t ev_lcuts = nullptr;   // nemo_min_label_cuts' level counts / round 1's words / totals / rows have reached pinned memory
-  hipEvent_t *const events[25] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_gcuts = nullptr;   // nemo_min_group_cuts' level counts / round 1's words / totals / rows have reached pinned memory
+  hipEvent_t *const events[26] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
-                                  &ev_cuts,    &ev_klabel,  &ev_lcuts};
+                                  &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts};
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -484,12 +512,14 @@ struct nemo_ctx {
   Pinned<uint32_t> h_cuts;   // nemo_min_cuts: counts, round 1's words and the candidates, the totals, then the rows
   Pinned<uint64_t> h_klabel;  // nemo_knockout_labels: the level counts; then the (lost, hit) words and the counts
   Pinned<uint32_t> h_lcuts;  // nemo_min_label_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
-  void **const pinned[26] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint32_t> h_gcuts;  // nemo_min_group_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
+  void **const pinned[27] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
-                             h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot()};
+                             h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot(),
+                             h_gcuts.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

@@ -273,6 +273,26 @@ void launch_lc_glob(const DevCorpus &c, const LcArgs &a, uint32_t grid, hipStrea
 void launch_lc_reduce(const LcArgs &a, hipStream_t s);
 void launch_lc_support(const LcArgs &a, hipStream_t s);
 
+// One round of nemo_min_group_cuts (k_gcuts.hip): a candidate is a group of labels, a hypothesis the set of `size`
+// live candidate positions of colex rank h, which removes the union of its groups.  `r` is the round as
+// nemo_min_label_cuts' kernels read it (k_lc_reduce and k_lc_support take it as it is; of its fields the sweeps
+// leave cand, n_cand, lmap and k1 alone: r.key / r.val / r.slots is the table label + 1 -> row of the n_dist
+// distinct labels the groups name).
+struct GcArgs {
+  LcArgs r;
+  const uint32_t *goff;      // [n_groups + 1] candidate position -> its first entry in grow
+  uint32_t *grow;            // [n_named] the groups' labels (k_gc_table reads them), then their rows (k_gc_rows, in place)
+  uint32_t n_named, n_dist;
+  uint32_t *n_rows;          // k_gc_table: the rows handed out so far (zeroed); n_dist at its end
+  const uint32_t *live;      // [K1] live position -> candidate position (null in round 1: every candidate is live)
+};
+void launch_gc_table(const GcArgs &a, hipStream_t s);  // the table and *n_rows are zero
+void launch_gc_rows(const GcArgs &a, hipStream_t s);
+// the workgroups of round `size`'s k_gc_lds resident on the device at lds_bytes of dynamic LDS (0: the query failed)
+uint32_t gc_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu);
+void launch_gc_lds(const DevCorpus &c, const GcArgs &a, uint32_t grid, hipStream_t s);  // a.r.lds_total bytes of LDS
+void launch_gc_glob(const DevCorpus &c, const GcArgs &a, uint32_t grid, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

@@ -11,6 +11,7 @@
 // hold a cut pair); k_cut_count / launch_scan / k_cut_emit (k_cuts.hip) turn the cut words into rows and
 // k_lc_support recounts a row's column, its n_lost.
 #include "device.h"
+#include "hit_list.h"
 #include "internal.h"
 #include "ko_sweep.h"
 #include "lcut_host.h"
@@ -27,19 +28,6 @@ __global__ __launch_bounds__(KO_BLOCK) void k_lc_table(LcArgs a) {
   while (atomicCAS(&a.key[h], 0u, label + 1u) != 0u) h = klabel::next_slot(h, a.slots);
   a.val[h] = p;
 }
-
-// A graph's hit list, u32 entries: [0 .. k1] the rows' offsets, then the rows' nodes.  The first `cap` entries
-// live in LDS behind the image, the others in the workgroup's region.
-struct LcList {
-  uint32_t *head, *spill;
-  uint32_t cap;
-  __device__ __forceinline__ uint32_t get(uint32_t i) const { return i < cap ? head[i] : spill[i - cap]; }
-  __device__ __forceinline__ void set(uint32_t i, uint32_t x) const {
-    if (i < cap) head[i] = x;
-    else spill[i - cap] = x;
-  }
-  __device__ __forceinline__ uint32_t add(uint32_t i) const { return i < cap ? atomicAdd(&head[i], 1u) : atomicAdd(&spill[i - cap], 1u); }
-};
 
 // the live position of node v's label in this round: LC_NONE if the node carries no label, the table does not hold
 // it, its candidate is not live, or (a.sinks) the node is no sink goal.  Behind the barrier that ends the staging.
@@ -88,38 +76,8 @@ __device__ __forceinline__ void lc_loop(const DevCorpus &c, const LcArgs &a, uin
         ls.head = reinterpret_cast<uint32_t *>(dyn + image);
         ls.cap = (a.lds_total - image) / 4u;
       }
-      for (uint32_t i = tid; i <= k1; i += KO_BLOCK) ls.set(i, 0u);
-      __threadfence_block();  // the entries in the region
-      __syncthreads();        // ... and the image: the rule bits and rows are read below
-      for (uint32_t v = tid; v < g.V; v += KO_BLOCK) {  // count per live position
-        const uint32_t lp = lc_live<LDS>(a, g, v, gv.label[v]);
-        if (lp != LC_NONE) ls.add(lp);
-      }
-      __threadfence_block();
-      __syncthreads();
-      if (wave == 0u) {  // exclusive scan of the k1 + 1 counts (the last one is 0: it becomes the total)
-        uint32_t carry = 0u;
-        for (uint32_t base = 0; base <= k1; base += 64u) {
-          const uint32_t i = base + lane;
-          const uint32_t x = i <= k1 ? ls.get(i) : 0u;
-          uint32_t incl = x;
-#pragma unroll
-          for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)incl, d);
-            if ((int)lane >= d) incl += y;
-          }
-          if (i <= k1) ls.set(i, carry + incl - x);
-          carry += (uint32_t)__shfl((int)incl, 63);
-        }
-      }
-      __threadfence_block();
-      __syncthreads();
-      for (uint32_t v = tid; v < g.V; v += KO_BLOCK) {  // scatter: a row's cursor ends at the next row's start
-        const uint32_t lp = lc_live<LDS>(a, g, v, gv.label[v]);
-        if (lp != LC_NONE) ls.set(k1 + 1u + ls.add(lp), v);
-      }
-      __threadfence_block();
-      __syncthreads();  // row p is now entries [p ? off[p - 1] : 0, off[p]) behind the offsets
+      // the graph's hit nodes by live position (hit_list.h): count, scan, scatter
+      hit_list_build(ls, g.V, k1, [&](uint32_t v) { return lc_live<LDS>(a, g, v, gv.label[v]); });
     }
     uint64_t *dead = g.dead;
     const uint32_t c_lo = klabel::range_lo(a.n_chunks, a.parts, part), c_hi = klabel::range_lo(a.n_chunks, a.parts, part + 1u);

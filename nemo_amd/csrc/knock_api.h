@@ -1,8 +1,10 @@
 // knock_api.h — the host code the knock-out family's calls share (api_knock.hip, api_cuts.hip, api_klabel.hip,
-// api_lcuts.hip): the wait for a call's copies to pinned memory, the dynamic LDS of a persistent LDS-tier launch,
-// the listed graphs' split into the two tiers (api_klabel.hip, api_lcuts.hip), and the rounds' sizes and the rows
-// of the two cut searches (api_cuts.hip, api_lcuts.hip).  Every call keeps its own event, pinned buffer, device
-// buffers and state (ctx.h); nothing here owns any.  GroupTimer and grow_group are ctx.h's.
+// api_lcuts.hip, api_gcuts.hip): the wait for a call's copies to pinned memory, the dynamic LDS of a persistent
+// LDS-tier launch, the listed graphs' split into the two tiers (api_klabel.hip, api_lcuts.hip, api_gcuts.hip), and the
+// rounds' sizes and the rows of the three cut searches (api_cuts.hip, api_lcuts.hip, api_gcuts.hip), and the rounds'
+// limits, launch plans and driver of the two searches by label (api_lcuts.hip, api_gcuts.hip).  Every call keeps
+// its own event, pinned buffer, device buffers and state (ctx.h); nothing here owns any.  GroupTimer and grow_group
+// are ctx.h's.
 #pragma once
 #include <functional>
 
@@ -91,6 +93,102 @@ static inline Tiers split_tiers(const nemo_ctx *c, std::vector<uint32_t> &desc, 
     else desc[n + t.n_lds + gl++] = (uint32_t)i;
   }
   return t;
+}
+
+// ---- the rounds of a cut search by label across runs (nemo_min_label_cuts, nemo_min_group_cuts) --------------
+// A round's two limits (lcut_host.h) with the calling entry point's name and what it tells the caller to shorten.
+static inline int label_round_limit(nemo_ctx *c, const char *who, const char *shorten, size_t n, uint64_t k, uint32_t sz) {
+  switch (lcuts::round_check(n, k, sz)) {
+    case lcuts::ROUND_HYPS:
+      return fail(c, NEMO_ERR_LIMIT, "%s: the sets of %u of %llu live candidates exceed 2^32 - 2 hypotheses: shorten the %s or the run list", who,
+                  sz, (unsigned long long)k, shorten);
+    case lcuts::ROUND_WORDS:
+      return fail(c, NEMO_ERR_LIMIT, "%s: %zu list positions x %llu chunks of 64 sets of %u exceed 2^28 words: shorten the %s or the run list",
+                  who, n, (unsigned long long)cuts::chunks(cuts::round_hyps(k, sz)), sz, shorten);
+    default:
+      return NEMO_OK;
+  }
+}
+
+struct LabelPlan {  // one round's launches
+  uint32_t lds_total = 0;
+  uint64_t rw_lds = 0, rw_glob = 0;  // region words of a workgroup
+  uint64_t r_lds = 1, r_glob = 1;    // most workgroups
+};
+
+// The rounds' LDS and what a workgroup keeps in device memory, for a hit list of `rows` rows (rows + 1 + V entries,
+// lcut_host.h) behind the image.  resident(size, bytes): the resident workgroups of round `size`'s LDS-tier kernel;
+// lds_static: its static LDS.  *reg_need: the u64 words of all regions of the largest launch.
+template <class R>
+static int label_plans(nemo_ctx *c, const char *who, const char *kernel, R &&resident, const std::vector<uint32_t> &desc, size_t n,
+                       const Tiers &tr, uint64_t rows, uint32_t lds_static, uint32_t max_size, LabelPlan *plan, uint64_t *reg_need) {
+  const CorpusState &cs = c->cs;
+  const uint32_t cap = c->opt.kl_grid;
+  *reg_need = 1;
+  for (uint32_t sz = 1; sz <= max_size; sz++) {
+    LabelPlan &p = plan[sz - 1];
+    uint32_t res_lds = 1;
+    if (tr.n_lds) {
+      if (int rc = ko_lds_total(c, who, kernel, [&](uint32_t b) { return resident(sz, b); }, tr.image, 4 * lcuts::list_entries(rows, tr.lds_v),
+                                lds_static, &p.lds_total, &res_lds))
+        return rc;
+      for (size_t k = 0; k < tr.n_lds; k++) {
+        const uint32_t g = desc[desc[n + k]];
+        p.rw_lds = std::max(p.rw_lds, lcuts::region_words(0, lcuts::list_entries(rows, cs.nv(g)), (p.lds_total - tier_image(c, g)) / 4u));
+      }
+    }
+    p.rw_glob = lcuts::region_words(knock::dead_words(tr.glob_v), lcuts::list_entries(rows, tr.glob_v), 0);
+    p.r_lds = klabel::region_grid(res_lds, p.rw_lds), p.r_glob = klabel::region_grid(2ull * cs.dc.n_cu, p.rw_glob);
+    if (cap) p.r_lds = std::min<uint64_t>(p.r_lds, cap), p.r_glob = std::min<uint64_t>(p.r_glob, cap);
+    if (tr.n_lds) *reg_need = std::max(*reg_need, p.r_lds * p.rw_lds);
+    if (tr.n_glob) *reg_need = std::max(*reg_need, p.r_glob * p.rw_glob);
+  }
+  return NEMO_OK;
+}
+
+// One round: the two tiers' sweeps, then k_lc_reduce.  r: the round (size, n, n_hyp, n_chunks and the buffers set);
+// d_desc: the device copy of desc.  launch_lds(grid) / launch_glob(grid) launch the call's own sweep on r, timed
+// under lds_name / glob_name.  The byte model: a work item reads its graph's image (4 E + 12 V + 4 L + 8) and its
+// 4 V labels twice (count, scatter); a chunk writes 8 bytes (round 1: 16) and reads chunk_bytes more (the call's own:
+// what its 64 sets name); ops = E child words per chunk, an upper bound (the host does not know which chunks hit
+// nothing and skip the sweep); the global tier adds 16 V per chunk for its dead words in device memory.  The
+// reduction reads every word once and writes one per chunk.
+template <class LL, class LG>
+static int label_round(nemo_ctx *c, const LabelPlan &p, const Tiers &tr, const std::vector<uint32_t> &desc, nemo::LcArgs &r,
+                       const uint32_t *d_desc, double chunk_bytes, const char *lds_name, const char *glob_name, LL &&launch_lds,
+                       LG &&launch_glob, double *bytes, double *ops) {
+  if (!r.n_chunks) return NEMO_OK;
+  const CorpusState &cs = c->cs;
+  const uint32_t cap = c->opt.kl_grid, n = r.n;
+  const uint64_t ck = r.n_chunks;
+  const double per_word = r.size == 1 ? 16.0 : 8.0;
+  for (int tier = 0; tier < 2; tier++) {
+    const uint32_t nt = tier ? tr.n_glob : tr.n_lds;
+    if (!nt) continue;
+    const uint64_t res = tier ? p.r_glob : p.r_lds;
+    const klabel::Split sp = klabel::split(nt, ck, res);
+    const uint32_t grid = klabel::grid(sp.items, res, cap);
+    double b = 0, o = 0;
+    for (uint32_t k = 0; k < nt; k++) {
+      const uint32_t g = desc[desc[n + (tier ? tr.n_lds : 0) + k]];
+      const double V = (double)cs.nv(g), E = (double)cs.ne(g), L = (double)cs.kl_nlev[g];
+      b += sp.parts * (4.0 * E + 12.0 * V + 4.0 * L + 8.0 + 8.0 * V) + (double)ck * (per_word + chunk_bytes + (tier ? 16.0 * V : 0.0));
+      o += (double)ck * E;
+    }
+    r.pos = d_desc + n + (tier ? tr.n_lds : 0);
+    r.n_tier = nt, r.parts = sp.parts;
+    r.lds_total = tier ? 0u : p.lds_total;
+    r.region_words = tier ? p.rw_glob : p.rw_lds;
+    r.dead_words = tier ? knock::dead_words(tr.glob_v) : 0;
+    int rc;
+    if (tier) rc = timed(c, glob_name, b, o, [&] { launch_glob(grid); });
+    else rc = timed(c, lds_name, b, o, [&] { launch_lds(grid); });
+    if (rc) return rc;
+    *bytes += b, *ops += o;
+  }
+  const double b_red = per_word * (double)n * (double)ck + per_word * (double)ck;
+  *bytes += b_red;
+  return timed(c, "k_lc_reduce", b_red, 0, [&] { nemo::launch_lc_reduce(r, c->stream); });
 }
 
 // ---- the rounds and the rows of a cut search (nemo_min_cuts, nemo_min_label_cuts) -----------------------

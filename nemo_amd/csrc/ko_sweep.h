@@ -1,4 +1,4 @@
-// ko_sweep.h — what the knock-out family's kernels (k_knock.hip, k_cuts.hip, k_klabel.hip, k_lcuts.hip) share: a raw
+// ko_sweep.h — what the knock-out family's kernels (k_knock.hip, k_cuts.hip, k_klabel.hip, k_lcuts.hip, k_gcuts.hip) share: a raw
 // provenance graph as the sweep reads it, its LDS image and its global-tier form, the zeroing of the dead words, the
 // level sweep itself, which does not know where the seeds of its 64 hypotheses came from, the "lost" word of a swept
 // chunk, the count of a wave's bit columns, and on the host side the residency query and the dispatch on a round's

@@ -47,6 +47,8 @@ CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (3,))])
 KL_SINKS = 1  # NEMO_KL_SINKS
 # struct nemo_label_cut (nemo_fetch_min_label_cuts)
 LABEL_CUT_DTYPE = np.dtype([("size", np.uint32), ("label", np.uint32, (3,))])
+# struct nemo_group_cut (nemo_fetch_min_group_cuts)
+GROUP_CUT_DTYPE = np.dtype([("size", np.uint32), ("group", np.uint32, (3,))])
 
 
 def header_symbols() -> List[str]:
@@ -131,6 +133,9 @@ def lib():
             "nemo_min_label_cuts": ([vp, vp, sz, i32, vp, sz, u32, u32, u32], i32),
             "nemo_fetch_min_label_cuts": ([vp, vp, vp, u64, P(u64)], i32),
             "nemo_fetch_min_label_cut_stats": ([vp, vp], i32),
+            "nemo_min_group_cuts": ([vp, vp, sz, i32, vp, vp, sz, u32, u32, u32], i32),
+            "nemo_fetch_min_group_cuts": ([vp, vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_min_group_cut_stats": ([vp, vp], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -487,6 +492,47 @@ class Engine:
         hypotheses evaluated, minimal cuts found)."""
         out = np.zeros(9, np.uint64)
         self._chk(self.L.nemo_fetch_min_label_cut_stats(self.h, _p(out)))
+        return out.reshape(3, 3)
+
+    def min_group_cuts(self, iters: Sequence[int], cond: int, groups, max_size: int = 2, min_runs: int = 0,
+                       sinks_only: bool = False):
+        """nemo_min_group_cuts: min_label_cuts with groups of labels as candidates (a fault event that removes many
+        labels at once, nemo_amd.faults.fault_events): all minimal sets of <= max_size (1..3) candidates whose loss
+        together defeats the outcome on at least min_runs of the listed runs' pre (cond 0) or post (cond 1) graphs
+        (0: on every list position).  groups: a list of label lists, or a pair (group_off u64 [n_groups + 1],
+        group_labels u32), as knockout_labels takes its sets.  A set removes every node of a graph whose label one
+        of its groups names (sinks_only: every sink goal).  Returns (rows, n_lost): rows a structured array
+        (GROUP_CUT_DTYPE: size, group[3] the candidate positions, ascending, unused entries UINT32_MAX) sorted by
+        (size, colex rank of the live positions), n_lost[k] the list positions on which row k is lost;
+        min_group_cut_stats() has the rounds' counts."""
+        if isinstance(groups, tuple) and len(groups) == 2 and isinstance(groups[0], np.ndarray):
+            off = np.ascontiguousarray(groups[0], dtype=np.uint64)
+            labels = np.ascontiguousarray(groups[1], dtype=np.uint32)
+            n_groups = max(len(off) - 1, 0)
+        else:
+            n_groups = len(groups)
+            off = np.zeros(n_groups + 1, np.uint64)
+            off[1:] = np.cumsum([len(x) for x in groups], dtype=np.uint64)
+            labels = np.ascontiguousarray([v for x in groups for v in x], dtype=np.uint32)
+        it = np.ascontiguousarray(iters, dtype=np.uint32)
+        keep = labels if len(labels) else np.zeros(1, np.uint32)  # an empty list is a list: never NULL
+        self._chk(self.L.nemo_min_group_cuts(self.h, _p(it), len(it), int(cond), off.ctypes.data, _p(keep), n_groups, int(max_size),
+                                             int(min_runs), KL_SINKS if sinks_only else 0))
+        return self.min_group_cut_rows()
+
+    def min_group_cut_rows(self):
+        """nemo_fetch_min_group_cuts: (rows, n_lost) of the last min_group_cuts call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_min_group_cuts(self.h, None, None, 0, ctypes.byref(n)))
+        out, n_lost = np.zeros(n.value, GROUP_CUT_DTYPE), np.zeros(n.value, np.uint32)
+        self._chk(self.L.nemo_fetch_min_group_cuts(self.h, _p(out), _p(n_lost), len(out), ctypes.byref(n)))
+        return out, n_lost
+
+    def min_group_cut_stats(self) -> np.ndarray:
+        """nemo_fetch_min_group_cut_stats: a 3 x 3 u64 array, row s - 1 = (live candidates entering round s,
+        hypotheses evaluated, minimal cuts found)."""
+        out = np.zeros(9, np.uint64)
+        self._chk(self.L.nemo_fetch_min_group_cut_stats(self.h, _p(out)))
         return out.reshape(3, 3)
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
