@@ -162,6 +162,14 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       (default: 1024 when >= 1/8 of the graphs have >= 64k nodes)
  *   "stage_blocks"      nemo_stage_simplified's bulk copies: 0 = runtime copies
  *                       (default), else a copy kernel on this many workgroups
+ *   "stage_slices"      nemo_stage_simplified packs and copies the node state in this
+ *                       many slices (1..8, default 2), each slice's copy queued behind
+ *                       that slice's kernel only; 1 = one kernel and one copy
+ *   "stage_slice_ratio" each slice of the node state this many times the one before
+ *                       (1..8, default 4; 1 = equal slices): a short first slice puts
+ *                       the link to work sooner
+ *   "stage_pair_slices" the same for the chain pairs, in equal slices of the pair
+ *                       indices (1..8, default 1)
  *   "stage_sdma"        request nemo_stage_simplified's runtime copies as NoCU
  *                       (SDMA) copies (1) or plain D2H copies (0, default)
  *   "stage_cus"         CUs the copy stream's blit kernels may use (default 8,

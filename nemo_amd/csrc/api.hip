@@ -156,6 +156,8 @@ void nemo_ctx_destroy(nemo_ctx *c) {
   for (auto &p : c->pending) ev.insert(ev.end(), {p.a, p.b});
   ev.insert(ev.end(), c->ev_up.begin(), c->ev_up.end());
   for (hipEvent_t *e : c->events) ev.push_back(*e);
+  ev.insert(ev.end(), c->ev_state, c->ev_state + NEMO_STAGE_SLICES_MAX);
+  ev.insert(ev.end(), c->ev_ready, c->ev_ready + NEMO_STAGE_SLICES_MAX);
   for (hipEvent_t e : ev)
     if (e) hipEventDestroy(e);
   for (void **h : c->pinned)
@@ -186,6 +188,8 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
   }
   tiers_reset(c);  // any option may move graphs between tiers
   c->cs.ms_fused = false;  // ... and the fused tail's graphs were chosen under the old caps
+  // the hand-over orders itself behind everything queued so far again, not behind nemo_simplify's events
+  c->cs.flags_final = c->cs.chains_final = false;
   if (!strcmp(name, "chains_lds_max")) {
     c->opt.hcap_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.hcap_limit = c->opt.hcap_limit;
@@ -236,6 +240,18 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
   }
   if (!strcmp(name, "stage_blocks")) {
     c->opt.stage_blocks = value < 0 ? 0u : (uint32_t)value;
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "stage_slices")) {  // 1..8 slices of the node state, each with its own copy
+    c->opt.stage_slices = stage::clamp_slices(value, NEMO_STAGE_SLICES_DEFAULT);
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "stage_pair_slices")) {  // ... and of the chain pairs
+    c->opt.stage_pair_slices = stage::clamp_slices(value, NEMO_STAGE_PAIR_SLICES_DEFAULT);
+    return NEMO_OK;
+  }
+  if (!strcmp(name, "stage_slice_ratio")) {  // 1: equal state slices; r: each r times the one before
+    c->opt.stage_ratio = value < 0 ? NEMO_STAGE_RATIO_DEFAULT : (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), NEMO_STAGE_RATIO_MAX);
     return NEMO_OK;
   }
   if (!strcmp(name, "chains_glob_block")) {  // 0 (by corpus), 256 or 512; takes effect at the next load
@@ -1107,6 +1123,7 @@ int nemo_simplify(nemo_ctx *c) {
   if (chain_tiers) c->cs.tiers_run |= 2u;
   if ((rc = ensure_event(c, &c->ev_simp))) return rc;
   HIPCHK(c, hipEventRecord(c->ev_simp, c->stream));  // a simplified pull on `aux` starts here
+  c->cs.chains_final = true;  // ... and the staged chain pairs (nemo_stage_simplified)
   c->cs.simplified = true;
   c->cs.protos_done = false;
   return NEMO_OK;

@@ -142,25 +142,34 @@ static hipError_t stage_copy(nemo_ctx *c, void *dst, const void *src, size_t n) 
   return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->copy);
 }
 
-// The 2-bit node state on stream s and its copy; s has reached the point where the flags are final.
-static int stage_state(nemo_ctx *c, hipStream_t s) {
+// The 2-bit node state on stream s and its copy, in K slices of whole words, each stage_ratio times the
+// one before; s has reached the point where the flags are final.  Each slice's copy waits for that
+// slice's k_pack_state only, so the link starts behind the first, short slice; an empty slice (fewer
+// words than slices) issues nothing, but the last.
+static int stage_state(nemo_ctx *c, hipStream_t s, uint32_t K) {
   int rc;
-  const uint64_t sbytes = 4 * ((c->cs.V + 15) / 16);  // 2-bit node state
+  const uint64_t words = stage::state_words(c->cs.V), sbytes = 4 * words;  // 2-bit node state
   if ((rc = c->cs.d_state.grow(c, sbytes / 4 + 1))) return rc;
-  rc = timed_on(c, s, "k_pack_state", (double)c->cs.V + (double)sbytes, 0,
-                [&] { nemo::launch_pack_state(c->cs.dc.flags, c->cs.d_state.p, c->cs.V, s); });
-  if (rc) return rc;
   if ((rc = c->h_flags.grow(c, sbytes + 16))) return rc;
-  if ((rc = ensure_event(c, &c->ev_state))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev_state, s));
-  HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_state, 0));
-  HIPCHK(c, stage_copy(c, c->h_flags.p, c->cs.d_state.p, sbytes));
+  for (uint32_t k = 0; k < K; k++) {
+    const stage::Range w = stage::slice(words, K, k, c->opt.stage_ratio);
+    if (w.empty() && k + 1 < K) continue;
+    rc = timed_on(c, s, "k_pack_state", (double)stage::state_nodes(c->cs.V, w) + 4.0 * (double)w.size(), 0,
+                  [&] { nemo::launch_pack_state(c->cs.dc.flags, c->cs.d_state.p, c->cs.V, w.lo, w.size(), s); });
+    if (rc) return rc;
+    if ((rc = ensure_event(c, &c->ev_state[k]))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_state[k], s));
+    HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_state[k], 0));
+    HIPCHK(c, stage_copy(c, c->h_flags.p + 4 * w.lo, c->cs.d_state.p + w.lo, 4 * w.size()));
+  }
   return NEMO_OK;
 }
 
-// Enqueue the chain pairs at a capacity of `cap` pairs and their bulk copy on the copy stream
-// (behind the node state's, which stage_state queued first).
-static int stage_enqueue(nemo_ctx *c, uint64_t cap) {
+// Enqueue the chain pairs at a capacity of `cap` pairs, in K slices of the pair indices, and their bulk
+// copies on the copy stream (behind the node state's, which stage_state queued first).  Each slice's
+// copy waits for that slice's k_chain_pairs only; the offsets' copy and ev_copied follow the last slice,
+// which is issued even when it is empty.
+static int stage_enqueue(nemo_ctx *c, uint64_t cap, uint32_t K) {
   int rc;
   hipStream_t s = c->cs.stage_stream ? c->cs.stage_stream : c->stream;
   const uint64_t pw = c->cs.pairs_wide ? 2 : 1;  // u32 words per pair
@@ -168,14 +177,21 @@ static int stage_enqueue(nemo_ctx *c, uint64_t cap) {
     HIPCHK(c, hipStreamSynchronize(s));
     if ((rc = c->cs.d_chht.grow(c, pw * cap + 2))) return rc;
   }
-  rc = timed_on(c, s, "k_chain_pairs", 4.0 * pw * (double)cap + 20.0 * c->cs.G, 0,
-                [&] { nemo::launch_chain_pairs(c->cs.dc, c->cs.d_choff.p, c->cs.d_chht.p, cap, c->cs.pairs_wide ? 1 : 0, s); });
-  if (rc) return rc;
   if ((rc = c->h_chht.grow(c, pw * cap + 2))) return rc;
-  nemo::launch_to_host(c->h_choff.p, c->cs.d_choff.p, ((size_t)c->cs.G + 1) * 8, s);
-  HIPCHK(c, hipEventRecord(c->ev_ready, s));
-  HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_ready, 0));
-  HIPCHK(c, stage_copy(c, c->h_chht.p, c->cs.d_chht.p, pw * cap * 4));
+  for (uint32_t k = 0; k < K; k++) {
+    const stage::Range r = stage::slice(cap, K, k);
+    const bool last = k + 1 == K;
+    if (r.empty() && !last) continue;
+    rc = timed_on(c, s, "k_chain_pairs", 4.0 * pw * (double)r.size() + (last ? 20.0 * c->cs.G : 0.0), 0, [&] {
+      nemo::launch_chain_pairs(c->cs.dc, c->cs.d_choff.p, c->cs.d_chht.p, r.lo, r.hi, c->cs.pairs_wide ? 1 : 0, s);
+    });
+    if (rc) return rc;
+    if (last) nemo::launch_to_host(c->h_choff.p, c->cs.d_choff.p, ((size_t)c->cs.G + 1) * 8, s);
+    if ((rc = ensure_event(c, &c->ev_ready[k]))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_ready[k], s));
+    HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_ready[k], 0));
+    HIPCHK(c, stage_copy(c, c->h_chht.p + pw * r.lo, c->cs.d_chht.p + pw * r.lo, pw * r.size() * 4));
+  }
   HIPCHK(c, hipEventRecord(c->ev_copied, c->copy));
   c->cs.staged_cap = cap;
   return NEMO_OK;
@@ -203,7 +219,9 @@ int nemo_stage_simplified(nemo_ctx *c) {
     }
     if (!c->copy) HIPCHK(c, hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
   }
-  if ((rc = ensure_event(c, &c->ev_ready)) || (rc = ensure_event(c, &c->ev_copied))) return rc;
+  if ((rc = ensure_event(c, &c->ev_copied))) return rc;
+  const uint32_t K = std::min(std::max(c->opt.stage_slices, 1u), NEMO_STAGE_SLICES_MAX);
+  const uint32_t KP = std::min(std::max(c->opt.stage_pair_slices, 1u), NEMO_STAGE_SLICES_MAX);
   if (c->cs.staged) HIPCHK(c, hipEventSynchronize(c->ev_copied));  // host buffers are reused
   c->cs.staged = false;
   if ((rc = c->cs.d_choff.grow(c, (uint64_t)c->cs.G + 1))) return rc;
@@ -211,18 +229,22 @@ int nemo_stage_simplified(nemo_ctx *c) {
   if (c->opt.stage_on_aux) {  // read-only on the analysis: `stream` goes on to the triggers and pulls
     if (!c->aux) HIPCHK(c, hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
     // the node state from where nemo_simplify's flags were final (beside the chain cover), then
-    // the chain pairs from here (the chain cover and whatever the caller queued since)
+    // the chain pairs from where its chains were (ev_simp: beside whatever the caller queued since)
     if (!c->cs.flags_final) {  // flags rewritten since nemo_simplify: pack them where `stream` is now
       if ((rc = ensure_event(c, &c->ev_flags))) return rc;
       HIPCHK(c, hipEventRecord(c->ev_flags, c->stream));
     }
     HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_flags, 0));
-    if ((rc = stage_state(c, c->aux))) return rc;
-    if ((rc = ensure_event(c, &c->ev_stage))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_stage, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_stage, 0));
+    if ((rc = stage_state(c, c->aux, K))) return rc;
+    if (c->cs.chains_final) {
+      HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_simp, 0));
+    } else {  // chain or nch may have been rewritten since nemo_simplify: behind everything queued so far
+      if ((rc = ensure_event(c, &c->ev_stage))) return rc;
+      HIPCHK(c, hipEventRecord(c->ev_stage, c->stream));
+      HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_stage, 0));
+    }
     s = c->aux;
-  } else if ((rc = stage_state(c, s))) {
+  } else if ((rc = stage_state(c, s, K))) {
     return rc;
   }
   c->cs.stage_stream = s;
@@ -231,6 +253,7 @@ int nemo_stage_simplified(nemo_ctx *c) {
   // the pair count is only known on the device: stage at the last count seen
   // (no host round trip); nemo_simplified_view re-stages if it was too small
   uint64_t cap = c->cs.chht_hint;
+  const bool counted = !cap;  // the first stage after a load: the count comes back first, one slice
   if (!cap) {
     if ((rc = ensure_event(c, &c->ev_misc))) return rc;
     nemo::launch_to_host(c->h_choff.p, c->cs.d_choff.p, ((size_t)c->cs.G + 1) * 8, s);
@@ -238,7 +261,7 @@ int nemo_stage_simplified(nemo_ctx *c) {
     HIPCHK(c, hipEventSynchronize(c->ev_misc));
     cap = c->h_choff.p[c->cs.G];
   }
-  if ((rc = stage_enqueue(c, cap))) return rc;
+  if ((rc = stage_enqueue(c, cap, counted ? 1u : KP))) return rc;
   c->cs.staged = true;
   return NEMO_OK;
 }
@@ -256,7 +279,7 @@ int nemo_simplified_view(nemo_ctx *c, const uint8_t **state, const uint64_t **ch
     // on the context's stream, behind everything queued since the first stage (work that
     // rewrites flags may follow it there; `aux` was ordered only after the first stage)
     c->cs.stage_stream = c->stream;
-    int rc = stage_enqueue(c, n);
+    int rc = stage_enqueue(c, n, 1);
     if (rc) return rc;
     HIPCHK(c, hipEventSynchronize(c->ev_copied));
   }

@@ -26,6 +26,7 @@
 #include "nearest_host.h"
 #include "node.h"
 #include "pairs_host.h"
+#include "stage_host.h"
 
 struct Agg {
   uint64_t launches = 0;
@@ -144,6 +145,11 @@ struct Options {
   uint32_t pull_on_aux = 0;
   uint32_t stage_on_aux = 1;  // the hand-over kernels of nemo_stage_simplified on `aux` (option stage_aux)
   uint32_t stage_blocks = 0;  // bulk staging: 0 = runtime copies, else k_to_host on this many blocks
+  // nemo_stage_simplified packs and copies the node state in stage_slices slices, each stage_ratio times
+  // the one before, and the chain pairs in stage_pair_slices equal slices; each slice's copy behind that
+  // slice's kernel only (1: one kernel and one copy)
+  uint32_t stage_slices = NEMO_STAGE_SLICES_DEFAULT, stage_ratio = NEMO_STAGE_RATIO_DEFAULT;
+  uint32_t stage_pair_slices = NEMO_STAGE_PAIR_SLICES_DEFAULT;
   bool stage_sdma = false;    // runtime copies requested as NoCU (SDMA) copies (cleared if the runtime refuses)
   uint32_t stage_cus = 8;     // CUs of the copy stream (hipExtStreamCreateWithCUMask); 0 = unmasked
   int class_hash_bits = 128;  // nemo_diff_classes buckets by the low k bits of the hash (test knob: forces collisions)
@@ -440,6 +446,7 @@ struct CorpusState : GraphSizes {
 
   // staged simplification results
   bool flags_final = false;  // ev_flags marks the current flags (no flag-rewriting call since)
+  bool chains_final = false;  // ev_simp marks the current chain and nch (nothing that may rewrite them since)
   hipStream_t stage_stream = nullptr;  // the stream the last stage's hand-over kernels went on
   bool staged = false;
   uint64_t staged_n = 0, staged_cap = 0, chht_hint = 0;
@@ -472,7 +479,9 @@ struct nemo_ctx {
   hipEvent_t ev_protos = nullptr, ev_red = nullptr, ev_diff = nullptr, ev_misc = nullptr, ev_tiers = nullptr;
   // pinned upload staging is reused once the previous upload from the same buffer has landed
   hipEvent_t ev_up_hlab = nullptr, ev_up_succ = nullptr, ev_up_dsrc = nullptr;
-  hipEvent_t ev_ready = nullptr, ev_copied = nullptr;
+  // one per slice of the chain pairs (stage_pair_slices): the slice's pairs are on the device
+  hipEvent_t ev_ready[NEMO_STAGE_SLICES_MAX] = {};
+  hipEvent_t ev_copied = nullptr;  // the last slice's copy has landed: behind every other copy of the stage
   // a simplified pull on `aux` waits for the end of nemo_simplify (ev_simp) only, so it runs
   // beside the protos and hand-over kernels of `stream`; anything that rewrites its inputs
   // first waits for ev_auxpull
@@ -480,7 +489,8 @@ struct nemo_ctx {
   // recorded by nemo_simplify once the node flags are final (after the mark / clean / delete-set
   // kernels, before the chain cover, which only reads them): the staged 2-bit node state is
   // packed and copied from there on, beside the chain cover (nemo_stage_simplified)
-  hipEvent_t ev_flags = nullptr, ev_state = nullptr;
+  // (ev_state: one per slice of the state, recorded behind the slice's k_pack_state)
+  hipEvent_t ev_flags = nullptr, ev_state[NEMO_STAGE_SLICES_MAX] = {};
   // the hand-over kernels of nemo_stage_simplified on `aux`: behind everything `stream` has
   // queued so far, beside the triggers and pulls queued after
   hipEvent_t ev_stage = nullptr;
@@ -492,11 +502,12 @@ struct nemo_ctx {
   hipEvent_t ev_klabel = nullptr;  // nemo_knockout_labels' level counts / words / counts have reached pinned memory
   hipEvent_t ev_lcuts = nullptr;   // nemo_min_label_cuts' level counts / round 1's words / totals / rows have reached pinned memory
   hipEvent_t ev_gcuts = nullptr;   // nemo_min_group_cuts' level counts / round 1's words / totals / rows have reached pinned memory
-  hipEvent_t *const events[26] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
-                                  &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc, &ev_ready,
-                                  &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_state, &ev_stage,
+  hipEvent_t *const events[24] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+                                  &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc,
+                                  &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
                                   &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts};
+  // ... and the slices' (ev_state, ev_ready), destroyed with them
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
   // pinned result hand-over, written by k_to_host (device -> pinned host), and upload staging
@@ -634,6 +645,7 @@ static inline int ensure_event(nemo_ctx *c, hipEvent_t *e) {
 // Kernels that rewrite node flags must not overtake a staged copy still in flight.
 static inline int guard_staged(nemo_ctx *c) {
   c->cs.flags_final = false;  // the caller is about to rewrite node flags
+  c->cs.chains_final = false;  // ... and the chains with them, or the graphs under them
   if (c->cs.staged) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied, 0));
   if (c->cs.pull_aux_pending) {  // a pull on `aux` still reads the graphs, flags and chains
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_auxpull, 0));

@@ -400,9 +400,11 @@ uint32_t dx_scan_tiles(uint32_t n);  // tile sums launch_scan needs for n entrie
 void launch_scan(uint32_t *a, uint32_t n, uint32_t *tsum, hipStream_t s);  // in-place exclusive scan
 // rest: graphs (which 0/1) or g0 (which 2) past k_pull_lds's LDS tier, counted on the host
 void launch_pull(const DevCorpus &c, const PullArgs &a, uint32_t slots, uint32_t rest, hipStream_t s);
-void launch_chain_pairs(const DevCorpus &c, const uint64_t *off, uint32_t *out, uint64_t cap, int wide,
+// the pairs with index in [lo, hi), hi at most the capacity of `out` in pairs
+void launch_chain_pairs(const DevCorpus &c, const uint64_t *off, uint32_t *out, uint64_t lo, uint64_t hi, int wide,
                         hipStream_t s);
-void launch_pack_state(const uint8_t *flags, uint32_t *out, uint64_t V, hipStream_t s);
+// the state's words [w0, w0 + nw)
+void launch_pack_state(const uint8_t *flags, uint32_t *out, uint64_t V, uint64_t w0, uint64_t nw, hipStream_t s);
 void launch_chain_gather(const DevCorpus &c, uint64_t *off, uint32_t *out, hipStream_t s);
 void launch_triggers(const DevCorpus &c, const TrigArgs &a, int phase, hipStream_t s);
 void launch_goal_labels(const DevCorpus &c, uint32_t g, uint32_t *out, hipStream_t s);

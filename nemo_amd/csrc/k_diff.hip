@@ -1178,33 +1178,41 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_chain_gather(DevCorpus c, const 
 // (preprocessing.go:249-340 materialises exactly head.preds -> c -> tail.succs).
 // Pairs are (head, tail) u32 when `wide`, else packed head | tail << 16 (every
 // graph under 65536 nodes), halving the hand-over.
+// One launch writes the pairs with index in [lo, hi) only (a slice of the hand-over, hi at most the
+// buffer's capacity): a workgroup whose graph's pairs miss the range returns at once, one whose pairs
+// straddle an end writes its part.  Pairs past the capacity are written by no launch; the host
+// re-stages with the capacity off[G] asks for.
 __global__ __launch_bounds__(NEMO_BLOCK) void k_chain_pairs(DevCorpus c, const uint64_t *off, uint32_t *out,
-                                                             uint64_t cap, int wide) {
+                                                             uint64_t lo, uint64_t hi, int wide) {
   const uint32_t g = blockIdx.x;
-  const uint32_t n = c.nch[g];
-  if (off[g] + n > cap) return;  // the host re-stages with the capacity off[G] asks for
+  const uint64_t o = off[g], e = o + c.nch[g];
+  const uint64_t a = o > lo ? o : lo, b = e < hi ? e : hi;
+  if (a >= b) return;
+  const uint32_t k0 = (uint32_t)(a - o), k1 = (uint32_t)(b - o);
   const uint32_t *ch = c.chain + 5 * c.node_off[g];
   if (wide) {
-    uint2 *o = reinterpret_cast<uint2 *>(out) + off[g];
-    for (uint32_t k = threadIdx.x; k < n; k += NEMO_BLOCK) o[k] = make_uint2(ch[5 * k], ch[5 * k + 1]);
+    uint2 *p = reinterpret_cast<uint2 *>(out) + o;
+    for (uint32_t k = k0 + threadIdx.x; k < k1; k += NEMO_BLOCK) p[k] = make_uint2(ch[5 * k], ch[5 * k + 1]);
   } else {
-    uint32_t *o = out + off[g];
-    for (uint32_t k = threadIdx.x; k < n; k += NEMO_BLOCK) o[k] = ch[5 * k] | (ch[5 * k + 1] << 16);
+    uint32_t *p = out + o;
+    for (uint32_t k = k0 + threadIdx.x; k < k1; k += NEMO_BLOCK) p[k] = ch[5 * k] | (ch[5 * k + 1] << 16);
   }
 }
 
-void launch_chain_pairs(const DevCorpus &c, const uint64_t *off, uint32_t *out, uint64_t cap, int wide,
+void launch_chain_pairs(const DevCorpus &c, const uint64_t *off, uint32_t *out, uint64_t lo, uint64_t hi, int wide,
                         hipStream_t s) {
-  hipLaunchKernelGGL(k_chain_pairs, dim3(c.G), dim3(NEMO_BLOCK), 0, s, c, off, out, cap, wide);
+  hipLaunchKernelGGL(k_chain_pairs, dim3(c.G), dim3(NEMO_BLOCK), 0, s, c, off, out, lo, hi, wide);
 }
 
 // Node state for the host, 2 bits per node (4 per byte, node v at byte v/4):
 // bit 0 = the node survives into the simplified graph (KEPT, not DELETED),
-// bit 1 = condition_holds.  One thread packs 16 nodes into a u32.
+// bit 1 = condition_holds.  One thread packs 16 nodes into a u32; one launch
+// packs the words [w0, w0 + nw) (a slice of the hand-over).
 __global__ __launch_bounds__(NEMO_BLOCK) void k_pack_state(const uint8_t *__restrict__ flags, uint32_t *out,
-                                                            uint64_t V) {
-  const uint64_t w = (uint64_t)blockIdx.x * NEMO_BLOCK + threadIdx.x;
-  if (16 * w >= V) return;
+                                                            uint64_t V, uint64_t w0, uint64_t nw) {
+  const uint64_t i = (uint64_t)blockIdx.x * NEMO_BLOCK + threadIdx.x;
+  const uint64_t w = w0 + i;
+  if (i >= nw || 16 * w >= V) return;
   uint8_t f[16];
   if (16 * w + 16 <= V) {
     *reinterpret_cast<uint4 *>(f) = reinterpret_cast<const uint4 *>(flags)[w];
@@ -1221,11 +1229,10 @@ __global__ __launch_bounds__(NEMO_BLOCK) void k_pack_state(const uint8_t *__rest
   out[w] = x;
 }
 
-void launch_pack_state(const uint8_t *flags, uint32_t *out, uint64_t V, hipStream_t s) {
-  const uint64_t words = (V + 15) / 16;
-  if (!words) return;
-  hipLaunchKernelGGL(k_pack_state, dim3((uint32_t)((words + NEMO_BLOCK - 1) / NEMO_BLOCK)), dim3(NEMO_BLOCK), 0, s,
-                     flags, out, V);
+void launch_pack_state(const uint8_t *flags, uint32_t *out, uint64_t V, uint64_t w0, uint64_t nw, hipStream_t s) {
+  if (!nw) return;
+  hipLaunchKernelGGL(k_pack_state, dim3((uint32_t)((nw + NEMO_BLOCK - 1) / NEMO_BLOCK)), dim3(NEMO_BLOCK), 0, s,
+                     flags, out, V, w0, nw);
 }
 
 void launch_chain_gather(const DevCorpus &c, uint64_t *off, uint32_t *out, hipStream_t s) {
