@@ -1052,6 +1052,104 @@ func (n *Neo4J) MinGroupCuts(iters []uint, cond string, groups [][]uint32, maxSi
 	return res, stats, nil
 }
 
+// Witness is the surviving derivation of one graph under one fault hypothesis:
+// what is left of the outcome's provenance, and what it rests on.
+type Witness struct {
+	Graph      uint32  // 2*run + cond
+	Roots      uint32  // nodes of in-degree 0
+	RootsAlive uint32  // 0: the hypothesis defeats the outcome and the witness is empty
+	Nodes      uint32  // nodes of the witness
+	Sinks      uint32  // sink goals of the witness: the base events it rests on
+	Mask       []uint8 // withMasks: one byte per node of the graph, 1 = in the witness
+}
+
+func witnessFlags(all, withMasks bool) C.uint32_t {
+	var flags C.uint32_t
+	if all {
+		flags |= C.NEMO_WIT_ALL
+	}
+	if withMasks {
+		flags |= C.NEMO_WIT_MASKS
+	}
+	return flags
+}
+
+// witnessRows fetches the rows of the last witness call and, withMasks, every
+// hypothesis' mask; nodes(graph) is the node count of a graph.
+func (n *Neo4J) witnessRows(withMasks bool, nodes func(uint32) uint64) ([]*Witness, error) {
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_witness(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	rows := make([]C.nemo_witness, cnt+1)
+	if err := n.err(C.nemo_fetch_witness(n.ctx, &rows[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	res := make([]*Witness, cnt)
+	for h, w := range rows[:cnt] {
+		m := &Witness{Graph: uint32(w.graph), Roots: uint32(w.n_roots), RootsAlive: uint32(w.roots_alive), Nodes: uint32(w.n_nodes), Sinks: uint32(w.n_sinks)}
+		if withMasks {
+			m.Mask = make([]uint8, nodes(m.Graph)+1)
+			if err := n.err(C.nemo_fetch_witness_mask(n.ctx, C.uint64_t(h), (*C.uint8_t)(unsafe.Pointer(&m.Mask[0])), C.uint64_t(len(m.Mask)))); err != nil {
+				return nil, err
+			}
+			m.Mask = m.Mask[:len(m.Mask)-1]
+		}
+		res[h] = m
+	}
+	return res, nil
+}
+
+// WitnessSets answers what a fault hypothesis that is no cut leaves behind
+// (nemo_witness_sets): for every set of graph-local nodes removed from one
+// run's pre or post provenance, one derivation of every surviving root (all:
+// every surviving derivation) and the base events it rests on, which are the
+// events the next hypothesis must hit.  nodes is the graph's node count (for
+// the masks).
+func (n *Neo4J) WitnessSets(iter uint, cond string, sets [][]uint32, all bool, withMasks bool, nodes uint64) ([]*Witness, error) {
+	off := make([]C.uint64_t, len(sets)+1)
+	var ent []C.uint32_t
+	for k, set := range sets {
+		for _, v := range set {
+			ent = append(ent, C.uint32_t(v))
+		}
+		off[k+1] = C.uint64_t(len(ent))
+	}
+	ent = append(ent, 0) // never empty: &ent[0] below
+	if err := n.err(C.nemo_witness_sets(n.ctx, C.uint32_t(iter), condIndex(cond), &off[0], &ent[0], C.size_t(len(sets)), witnessFlags(all, withMasks))); err != nil {
+		return nil, err
+	}
+	return n.witnessRows(withMasks, func(uint32) uint64 { return nodes })
+}
+
+// WitnessLabels is WitnessSets with hypotheses that name interned labels,
+// against every listed run at once (nemo_witness_labels): row i*len(sets)+s is
+// set s on listed run i.  nodes(graph) is the node count of graph 2*run+cond
+// (for the masks; may be nil without them).
+func (n *Neo4J) WitnessLabels(iters []uint, cond string, sets [][]uint32, all bool, withMasks bool, sinksOnly bool, nodes func(uint32) uint64) ([]*Witness, error) {
+	its := make([]C.uint32_t, len(iters)+1)
+	for i, it := range iters {
+		its[i] = C.uint32_t(it)
+	}
+	off := make([]C.uint64_t, len(sets)+1)
+	var labels []C.uint32_t
+	for k, set := range sets {
+		for _, l := range set {
+			labels = append(labels, C.uint32_t(l))
+		}
+		off[k+1] = C.uint64_t(len(labels))
+	}
+	labels = append(labels, 0) // never empty: &labels[0] below
+	flags := witnessFlags(all, withMasks)
+	if sinksOnly {
+		flags |= C.NEMO_WIT_SINKS
+	}
+	if err := n.err(C.nemo_witness_labels(n.ctx, &its[0], C.size_t(len(iters)), condIndex(cond), &off[0], &labels[0], C.size_t(len(sets)), flags)); err != nil {
+		return nil, err
+	}
+	return n.witnessRows(withMasks, nodes)
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

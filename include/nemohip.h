@@ -270,7 +270,17 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       lists, once per graph, the nodes whose label some set names,
  *                       and a chunk of 64 sets probes its table with those alone.  0:
  *                       no list, every chunk probes with every node's label (same
- *                       results; the form the list was measured against, tested)    */
+ *                       results; the form the list was measured against, tested)
+ *   "wit_lds_max"       largest LDS image (bytes) of a graph nemo_witness_sets and
+ *                       nemo_witness_labels run in LDS; the image is the knock-out
+ *                       sweep's plus a second u64 word per node, so a graph of the
+ *                       same shape needs 8 V bytes more than under "knock_lds_max";
+ *                       graphs past it, and graphs of 65536 nodes or more, run over
+ *                       the CSR in device memory (default and upper bound 159744,
+ *                       one workgroup per CU past 81920, the fastest of the three
+ *                       points measured at the C3 shape; 0 = every graph in
+ *                       device memory; -1 = the default); takes effect at the
+ *                       next witness call; the grid cap is "kl_grid"'s            */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -790,6 +800,73 @@ int nemo_fetch_min_group_cuts(nemo_ctx *ctx, nemo_group_cut *out, uint32_t *n_lo
 /* As nemo_fetch_min_cut_stats: per size s = 1..3, out[3 (s - 1) ..]: live
  * candidates entering the round, hypotheses evaluated, minimal cuts found.     */
 int nemo_fetch_min_group_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
+
+/* ---- surviving derivations: why a run's outcome withstands a fault set ---------
+ * The other half of the knock-out family: where those calls say whether a fault
+ * set defeats the outcome, these say which derivation is left when it does not,
+ * and which base events that derivation rests on (the events the next fault
+ * hypothesis must hit).  The subject (a raw loaded graph g = 2r + cond),
+ * dead_F(v) and the roots (the nodes of in-degree 0) are the knock-out
+ * definitions above, unchanged.  alive = not dead.  Two facts follow from the
+ * definition and make the rest well defined: an alive rule has only alive
+ * children, and an alive goal with children has at least one alive child.
+ * For a hypothesis h with removed set F_h, need_h is defined top-down along the
+ * DUETO edges, roots first:
+ *   - a root is needed iff it is alive;
+ *   - a needed rule needs every child;
+ *   - a needed goal with children needs exactly one child, the alive child of
+ *     smallest node index; under NEMO_WIT_ALL it needs every alive child;
+ *   - a sink goal (a goal without children) needs nothing further.
+ * As in the knock-out definition all of this goes by the node's own kind and
+ * does not assume that goals and rules alternate.  W_h = {v : need_h(v)} is one
+ * derivation of every surviving root; under NEMO_WIT_ALL it is the whole
+ * surviving provenance, the union of all remaining derivations.  The loaded
+ * forward rows ascend by child index, so "smallest index" is "first alive child
+ * in row order", on both tiers.
+ * nemo_witness_sets takes explicit node sets on one graph: the arguments, the
+ * checks, the messages and the limits are nemo_knockout_sets'; hypothesis s is
+ * set s; NEMO_WIT_SINKS is NEMO_ERR_INVALID here.  nemo_witness_labels takes
+ * label sets against every listed run: F(i,s), the checks and the messages are
+ * nemo_knockout_labels' (NEMO_WIT_SINKS has NEMO_KL_SINKS' meaning: only sink
+ * goals match a label); the hypothesis index is i * n_sets + s.  Its limits, all
+ * NEMO_ERR_LIMIT with "tile the call": n * n_sets > 2^32 - 2, more than 2^28
+ * words (n list positions x chunks of 64 sets), more than 2^32 - 1 labels named,
+ * a hit list past 2^32 - 1 entries (distinct labels + 1 + V_g), or, with
+ * NEMO_WIT_MASKS, need words kept past 2^36 bytes (8 V_g bytes per list
+ * position and chunk of 64 sets; the node-set form has the same limit).
+ * Legal input that gives rows, not errors: the empty set (W is the derivation
+ * of the unharmed graph), a graph without roots (every count is 0), every root
+ * dead (roots_alive 0, W_h empty), a node or label named twice in a set, a label
+ * no listed node carries, a run listed twice (identical rows).  n_sets == 0 or
+ * n == 0 gives zero rows and NEMO_OK; an iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; cond outside 0 / 1 and unknown flags are NEMO_ERR_INVALID;
+ * a node context returns NEMO_ERR_STATE (single-device contexts only).
+ * Everything runs on the device on the context's stream (k_wit_lds / k_wit_glob:
+ * the knock-out sweep, then one more pass over the same levels, roots first);
+ * the calls block until the rows are on the host.  The result is the two calls'
+ * own state: valid until the next witness call or nemo_load_corpus (the fetches
+ * return NEMO_ERR_STATE otherwise), independent of every other call's state in
+ * both directions.  The tier is "wit_lds_max"'s, the grid cap "kl_grid"'s.      */
+typedef struct nemo_witness {
+  uint32_t graph;       /* 2r + cond                                                  */
+  uint32_t n_roots;     /* nodes of in-degree 0                                       */
+  uint32_t roots_alive; /* = roots in W_h; 0 means the outcome's every root is dead and W_h is empty */
+  uint32_t n_nodes;     /* |W_h|                                                      */
+  uint32_t n_sinks;     /* sink goals (no rule, empty forward row) in W_h: the base events W_h rests on */
+} nemo_witness;
+#define NEMO_WIT_ALL 1u   /* every surviving derivation, not one                       */
+#define NEMO_WIT_MASKS 2u /* keep the need words for nemo_fetch_witness_mask           */
+#define NEMO_WIT_SINKS 4u /* label form only: NEMO_KL_SINKS' meaning, only sink goals match a label */
+int nemo_witness_sets(nemo_ctx *ctx, uint32_t iteration, int cond, const uint64_t *set_off, const uint32_t *set_nodes,
+                      size_t n_sets, uint32_t flags);
+int nemo_witness_labels(nemo_ctx *ctx, const uint32_t *iters, size_t n, int cond, const uint64_t *set_off,
+                        const uint32_t *set_labels, size_t n_sets, uint32_t flags);
+/* out[h] for every hypothesis h; out == NULL queries *n_out.                    */
+int nemo_fetch_witness(nemo_ctx *ctx, nemo_witness *out, uint64_t cap, uint64_t *n_out);
+/* One byte per node of hypothesis hyp's graph, 1 = in W_h; cap >= V_g.  Needs a
+ * call with NEMO_WIT_MASKS (NEMO_ERR_STATE otherwise).  The column is taken on
+ * the host from the V need words of the hypothesis' chunk.                      */
+int nemo_fetch_witness_mask(nemo_ctx *ctx, uint64_t hyp, uint8_t *out, uint64_t cap);
 
 /* ---- corrections / extensions on run 0 (corrections.go:25-193, extensions.go:13-99)
  * pre rows (a, g, r) of findPreTriggers, post rows (g, r) of findPostTriggers,

@@ -359,6 +359,10 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.kl_hitlist = value != 0;
     return NEMO_OK;
   }
+  if (!strcmp(name, "wit_lds_max")) {  // largest LDS image (bytes) k_wit_lds takes; 0: every graph to k_wit_glob
+    c->opt.wit_lds_max = wit::lds_max_option(value);
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;

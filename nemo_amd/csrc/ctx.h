@@ -27,6 +27,7 @@
 #include "node.h"
 #include "pairs_host.h"
 #include "stage_host.h"
+#include "wit_host.h"
 
 struct Agg {
   uint64_t launches = 0;
@@ -165,6 +166,7 @@ struct Options {
   uint32_t cut_grid = 0;                      // test knob: most workgroups of k_cut_lds / k_cut_glob (0: as many as are resident)
   bool kl_hitlist = true;                     // option kl_hitlist 0: k_kl_lds probes every node's label per chunk (the measured alternative)
   uint32_t kl_grid = 0;                       // test knob: most workgroups of k_kl_lds / k_kl_glob (0: as many as are resident)
+  uint32_t wit_lds_max = WIT_LDS_DEFAULT;     // largest LDS image (bytes) k_wit_lds takes (0: every graph to k_wit_glob)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -411,6 +413,26 @@ struct CorpusState : GraphSizes {
   DevBuf<uint32_t> d_gcscan;         // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
   DevBuf<uint32_t> d_gcrows;         // [rows][4] nemo_group_cut, then [rows] n_lost
 
+  // surviving derivations (k_witness.hip): the two witness calls' own state, void after the next witness call or load;
+  // independent of knock-out, cut, label knock-out, label cut, group cut, diff, nearest and class state (kl_nlev above
+  // is the load's, not a result).  One group d_wt*, which grows only inside the two calls, each buffer to the largest
+  // request so far, behind a wait for the stream, in this order
+  bool wit_done = false, wit_masks = false;
+  uint64_t wit_n = 0, wit_sets = 0, wit_chunks = 0;  // list positions, sets and chunks of the last call
+  std::vector<uint32_t> wit_desc;    // the last call's uploads: [n] graphs | the LDS tier's list positions | the global tier's,
+  std::vector<uint64_t> wit_setoff;  // ... set offsets from the first set's,
+  std::vector<uint32_t> wit_ent;     // ... the label form's entries as rows, then the distinct labels,
+  std::vector<uint64_t> wit_moff;    // ... [n] list position -> its first kept need word
+  DevBuf<uint64_t> d_wtset;          // [sets + 1]
+  DevBuf<uint32_t> d_wtent;          // the sets' entries (nodes / rows), then the distinct labels
+  DevBuf<uint32_t> d_wtkey;          // the table's keys
+  DevBuf<uint32_t> d_wtval;          // ... and rows
+  DevBuf<uint32_t> d_wtdesc;         // [2 n]
+  DevBuf<uint64_t> d_wtmoff;         // [n]
+  DevBuf<uint32_t> d_wtrows;         // [n][sets][5] nemo_witness
+  DevBuf<uint64_t> d_wtneed;         // the kept need words (NEMO_WIT_MASKS)
+  DevBuf<uint64_t> d_wtreg;          // the workgroups' regions: k_wit_glob's dead and need words, the hit list's rest
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -502,11 +524,13 @@ struct nemo_ctx {
   hipEvent_t ev_klabel = nullptr;  // nemo_knockout_labels' level counts / words / counts have reached pinned memory
   hipEvent_t ev_lcuts = nullptr;   // nemo_min_label_cuts' level counts / round 1's words / totals / rows have reached pinned memory
   hipEvent_t ev_gcuts = nullptr;   // nemo_min_group_cuts' level counts / round 1's words / totals / rows have reached pinned memory
-  hipEvent_t *const events[24] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_wit = nullptr;     // the witness calls' level counts / rows have reached pinned memory
+  hipEvent_t *const events[25] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
-                                  &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts};
+                                  &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts,
+                                  &ev_wit};
   // ... and the slices' (ev_state, ev_ready), destroyed with them
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
@@ -524,13 +548,14 @@ struct nemo_ctx {
   Pinned<uint64_t> h_klabel;  // nemo_knockout_labels: the level counts; then the (lost, hit) words and the counts
   Pinned<uint32_t> h_lcuts;  // nemo_min_label_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
   Pinned<uint32_t> h_gcuts;  // nemo_min_group_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
-  void **const pinned[27] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint32_t> h_wit;    // the witness calls: the level counts; then the rows
+  void **const pinned[28] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
                              h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot(),
-                             h_gcuts.slot()};
+                             h_gcuts.slot(),  h_wit.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

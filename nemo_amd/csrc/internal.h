@@ -293,6 +293,38 @@ uint32_t gc_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu);
 void launch_gc_lds(const DevCorpus &c, const GcArgs &a, uint32_t grid, hipStream_t s);  // a.r.lds_total bytes of LDS
 void launch_gc_glob(const DevCorpus &c, const GcArgs &a, uint32_t grid, hipStream_t s);
 
+// One nemo_witness_sets / nemo_witness_labels call (k_witness.hip): the sets, in chunks of 64, are shared by every
+// listed graph (the node-set form lists one); hypothesis pos * n_sets + s is set s on list position pos.  A set's
+// entries are nodes (k1 == 0) or rows of the k1 distinct labels the sets name (the label form: key / val is the
+// table label + 1 -> row, klabel_host.h's hash).
+struct WitArgs {
+  const uint64_t *set_off;   // [n_sets + 1] offsets into ent
+  const uint32_t *ent;       // the sets' entries
+  uint32_t n_sets, n_chunks;
+  uint32_t k1;               // the label form: distinct labels (rows of a graph's hit list); 0: the entries are nodes
+  const uint32_t *dist;      // [k1] row -> label (k_wit_table)
+  uint32_t *key, *val;       // [slots] the table
+  uint64_t slots;
+  const uint32_t *graph;     // [n] list position -> graph
+  const uint32_t *pos;       // [n_tier] the launched tier's list positions
+  uint32_t n_tier;           // list positions of the launched tier
+  uint32_t parts;            // chunk ranges per graph (klabel::split)
+  uint32_t sinks;            // 1: only sink goals match a label (NEMO_WIT_SINKS)
+  uint32_t all;              // 1: a needed goal needs every alive child (NEMO_WIT_ALL)
+  uint32_t lds_total;        // k_wit_lds: the launch's dynamic LDS; what the image leaves holds the hit list's head
+  uint64_t *region;          // [workgroups][region_words] k_wit_glob's dead and need words, the hit list's rest
+  uint64_t region_words;     // u64 per workgroup
+  uint64_t glob_words;       // k_wit_glob: dead words, then need words at the region's start (the hit list follows)
+  uint32_t *rows;            // [n][n_sets][5] nemo_witness
+  uint64_t *need;            // NEMO_WIT_MASKS: the kept need words (null: none)
+  const uint64_t *moff;      // ... [n] list position -> its first word; chunk c's at c * dead_words(V)
+};
+void launch_wit_table(const WitArgs &a, hipStream_t s);  // the table is zero
+// the workgroups of k_wit_lds resident on the device at lds_bytes of dynamic LDS (0: the query failed)
+uint32_t wit_lds_resident(uint32_t lds_bytes, uint32_t n_cu);
+void launch_wit_lds(const DevCorpus &c, const WitArgs &a, uint32_t grid, hipStream_t s);  // a.lds_total bytes of LDS
+void launch_wit_glob(const DevCorpus &c, const WitArgs &a, uint32_t grid, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

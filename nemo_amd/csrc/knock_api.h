@@ -1,5 +1,5 @@
 // knock_api.h — the host code the knock-out family's calls share (api_knock.hip, api_cuts.hip, api_klabel.hip,
-// api_lcuts.hip, api_gcuts.hip): the wait for a call's copies to pinned memory, the dynamic LDS of a persistent
+// api_lcuts.hip, api_gcuts.hip, api_witness.hip): the wait for a call's copies to pinned memory, the dynamic LDS of a persistent
 // LDS-tier launch, the listed graphs' split into the two tiers (api_klabel.hip, api_lcuts.hip, api_gcuts.hip), and the
 // rounds' sizes and the rows of the three cut searches (api_cuts.hip, api_lcuts.hip, api_gcuts.hip), and the rounds'
 // limits, launch plans and driver of the two searches by label (api_lcuts.hip, api_gcuts.hip).  Every call keeps
@@ -78,21 +78,27 @@ struct Tiers {
 };
 
 // desc[0 .. n) are the listed graphs; desc[n .. 2 n) become the LDS tier's list positions, then the global tier's,
-// each in list order.
-static inline Tiers split_tiers(const nemo_ctx *c, std::vector<uint32_t> &desc, size_t n) {
+// each in list order.  fits(g) / image(g): the calling family's tier rule and LDS image (the witness calls keep a
+// second word array, wit_host.h).
+template <class F, class I>
+static inline Tiers split_tiers_by(const nemo_ctx *c, std::vector<uint32_t> &desc, size_t n, F &&fits, I &&image) {
   const CorpusState &cs = c->cs;
   Tiers t;
   for (size_t i = 0; i < n; i++) {
     const uint32_t g = desc[i];
-    if (tier_lds(c, g)) t.n_lds++, t.image = std::max(t.image, tier_image(c, g)), t.lds_v = std::max(t.lds_v, cs.nv(g));
+    if (fits(g)) t.n_lds++, t.image = std::max<uint32_t>(t.image, image(g)), t.lds_v = std::max(t.lds_v, cs.nv(g));
     else t.n_glob++, t.glob_v = std::max(t.glob_v, cs.nv(g));
   }
   uint32_t l = 0, gl = 0;
   for (size_t i = 0; i < n; i++) {
-    if (tier_lds(c, desc[i])) desc[n + l++] = (uint32_t)i;
+    if (fits(desc[i])) desc[n + l++] = (uint32_t)i;
     else desc[n + t.n_lds + gl++] = (uint32_t)i;
   }
   return t;
+}
+// ... by k_ko_lds's image and the option knock_lds_max
+static inline Tiers split_tiers(const nemo_ctx *c, std::vector<uint32_t> &desc, size_t n) {
+  return split_tiers_by(c, desc, n, [&](uint32_t g) { return tier_lds(c, g); }, [&](uint32_t g) { return tier_image(c, g); });
 }
 
 // ---- the rounds of a cut search by label across runs (nemo_min_label_cuts, nemo_min_group_cuts) --------------

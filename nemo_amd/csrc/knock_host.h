@@ -62,7 +62,7 @@ struct Chunk {
 static_assert(sizeof(Chunk) == 32, "two 16-byte loads");
 
 // dead words of one chunk: a word per node, whole 16-byte pairs
-static inline uint64_t dead_words(uint64_t V) { return (V + 1) & ~1ull; }
+KO_HD static inline uint64_t dead_words(uint64_t V) { return (V + 1) & ~1ull; }
 
 enum Limit { LIMIT_OK = 0, LIMIT_HYPS = 1, LIMIT_DEAD = 2 };
 

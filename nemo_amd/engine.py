@@ -49,6 +49,10 @@ KL_SINKS = 1  # NEMO_KL_SINKS
 LABEL_CUT_DTYPE = np.dtype([("size", np.uint32), ("label", np.uint32, (3,))])
 # struct nemo_group_cut (nemo_fetch_min_group_cuts)
 GROUP_CUT_DTYPE = np.dtype([("size", np.uint32), ("group", np.uint32, (3,))])
+# struct nemo_witness (nemo_fetch_witness)
+WITNESS_DTYPE = np.dtype([("graph", np.uint32), ("n_roots", np.uint32), ("roots_alive", np.uint32), ("n_nodes", np.uint32),
+                          ("n_sinks", np.uint32)])
+WIT_ALL, WIT_MASKS, WIT_SINKS = 1, 2, 4  # NEMO_WIT_ALL, NEMO_WIT_MASKS, NEMO_WIT_SINKS
 
 
 def header_symbols() -> List[str]:
@@ -136,6 +140,10 @@ def lib():
             "nemo_min_group_cuts": ([vp, vp, sz, i32, vp, vp, sz, u32, u32, u32], i32),
             "nemo_fetch_min_group_cuts": ([vp, vp, vp, u64, P(u64)], i32),
             "nemo_fetch_min_group_cut_stats": ([vp, vp], i32),
+            "nemo_witness_sets": ([vp, u32, i32, vp, vp, sz, u32], i32),
+            "nemo_witness_labels": ([vp, vp, sz, i32, vp, vp, sz, u32], i32),
+            "nemo_fetch_witness": ([vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_witness_mask": ([vp, u64, vp, u64], i32),
             "nemo_triggers": ([vp], i32),
             "nemo_fetch_triggers": ([vp, vp, u64, P(u64), vp, u64, P(u64), vp, u64, P(u64)], i32),
             "nemo_fetch_node_flags": ([vp, u32, u32, vp, u64], i32),
@@ -186,6 +194,70 @@ def unpin_corpus(pinned: list) -> None:
     L = lib()
     for a in pinned:
         L.nemo_host_unregister(a.ctypes.data)
+
+
+def _graph_rows(corpus: Corpus, g: int):
+    """(is_rule [V], children per node in ascending order) of graph g, from the host arrays"""
+    n0, n1 = int(corpus.node_off[g]), int(corpus.node_off[g + 1])
+    e0, e1 = int(corpus.edge_off[g]), int(corpus.edge_off[g + 1])
+    rule = (corpus.node_word[n0:n1] & np.uint32(0x80000000)) != 0
+    ch: List[List[int]] = [[] for _ in range(n1 - n0)]
+    for s, d in zip(corpus.edge_src[e0:e1].tolist(), corpus.edge_dst[e0:e1].tolist()):
+        ch[s].append(d)
+    for row in ch:
+        row.sort()
+    return rule, ch
+
+
+def witness_edges(corpus: Corpus, g: int, mask: np.ndarray, all: bool = False) -> np.ndarray:
+    """The edges of a witness W of graph g (mask: Engine.witness_mask's bytes), as [k, 2] local (source, target)
+    pairs sorted by (source, target): a rule in W keeps every forward edge, a goal in W the edge to its
+    smallest-index child in W, or under `all` (a mask of a NEMO_WIT_ALL call) every edge to a child in W.
+    witness_dot() turns them into a graph of nemo_amd.dot."""
+    rule, ch = _graph_rows(corpus, g)
+    out = []
+    for v in np.flatnonzero(np.asarray(mask[:len(ch)])).tolist():
+        if rule[v]:
+            out += [(v, c) for c in ch[v]]
+        else:
+            kept = [c for c in ch[v] if mask[c]]
+            out += [(v, c) for c in (kept if all else kept[:1])]
+    return np.asarray(out, dtype=np.uint32).reshape(-1, 2)
+
+
+def witness_support(corpus: Corpus, g: int, mask: np.ndarray):
+    """The base events a witness rests on: [(local node, label id, label string or None)] of the sink goals (goals
+    without children) of graph g that are in W, in node-index order."""
+    rule, ch = _graph_rows(corpus, g)
+    n0 = int(corpus.node_off[g])
+    out = []
+    for v in np.flatnonzero(np.asarray(mask[:len(ch)])).tolist():
+        if not rule[v] and not ch[v]:
+            lab = int(corpus.label[n0 + v])
+            out.append((v, lab, corpus.labels[lab] if corpus.labels is not None and lab < len(corpus.labels) else None))
+    return out
+
+
+def witness_dot(corpus: Corpus, g: int, mask: np.ndarray, all: bool = False):
+    """witness_edges as a nemo_amd.dot.DotGraph (create_dot's drawing of a pre / post graph), to stand beside the
+    diff graphs in a report."""
+    from .dot import ProvNode, create_dot
+    n0 = int(corpus.node_off[g])
+    cache: Dict[int, object] = {}
+
+    def node(i: int):
+        if i not in cache:
+            w = int(corpus.node_word[n0 + i])
+            is_rule = bool(w & 0x80000000)
+            lab = int(corpus.label[n0 + i])
+            label = corpus.labels[lab] if corpus.labels is not None and lab < len(corpus.labels) else str(lab)
+            table = corpus.tables[w & 0x00FFFFFF] if corpus.tables is not None else str(w & 0x00FFFFFF)
+            id_ = corpus.node_ids[n0 + i] if corpus.node_ids is not None else f"g{g}_n{i}"
+            typ = corpus.node_types[n0 + i] if is_rule and corpus.node_types is not None else None
+            cache[i] = ProvNode(id_, label, table, typ, None, is_rule)
+        return cache[i]
+
+    return create_dot([(node(int(s)), node(int(d))) for s, d in witness_edges(corpus, g, mask, all)], "pre" if g % 2 == 0 else "post")
 
 
 class Engine:
@@ -534,6 +606,52 @@ class Engine:
         out = np.zeros(9, np.uint64)
         self._chk(self.L.nemo_fetch_min_group_cut_stats(self.h, _p(out)))
         return out.reshape(3, 3)
+
+    def witness_sets(self, iteration: int, cond: int, sets: Sequence[Sequence[int]], all: bool = False, masks: bool = False) -> np.ndarray:
+        """nemo_witness_sets: the surviving derivation of one graph under explicit hypotheses, each a set of local
+        node indices removed by assumption (the empty set is legal).  Returns one WITNESS_DTYPE row per set (graph,
+        n_roots, roots_alive, n_nodes = |W|, n_sinks = the base events W rests on).  all: every surviving derivation
+        (NEMO_WIT_ALL), not the one that takes each goal's smallest alive child; masks: keep W for witness_mask()."""
+        off = np.zeros(len(sets) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in sets], dtype=np.uint64)
+        nodes = np.ascontiguousarray([v for x in sets for v in x], dtype=np.uint32)
+        self._chk(self.L.nemo_witness_sets(self.h, int(iteration), int(cond), off.ctypes.data, _p(nodes), len(sets),
+                                           (WIT_ALL if all else 0) | (WIT_MASKS if masks else 0)))
+        return self.witness_rows()
+
+    def witness_labels(self, iters: Sequence[int], cond: int, sets, all: bool = False, masks: bool = False,
+                       sinks_only: bool = False) -> np.ndarray:
+        """nemo_witness_labels: the surviving derivations of every listed run's pre (cond 0) or post (cond 1) graph
+        under hypotheses that name interned labels (sets: as knockout_labels takes them; sinks_only: only sink goals
+        match a label).  Returns the WITNESS_DTYPE rows, row i * n_sets + s = set s on list position i."""
+        if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+            off = np.ascontiguousarray(sets[0], dtype=np.uint64)
+            labels = np.ascontiguousarray(sets[1], dtype=np.uint32)
+            n_sets = max(len(off) - 1, 0)
+        else:
+            n_sets = len(sets)
+            off = np.zeros(n_sets + 1, np.uint64)
+            off[1:] = np.cumsum([len(x) for x in sets], dtype=np.uint64)
+            labels = np.ascontiguousarray([v for x in sets for v in x], dtype=np.uint32)
+        it = np.ascontiguousarray(iters, dtype=np.uint32)
+        self._chk(self.L.nemo_witness_labels(self.h, _p(it), len(it), int(cond), off.ctypes.data, _p(labels), n_sets,
+                                             (WIT_ALL if all else 0) | (WIT_MASKS if masks else 0) | (WIT_SINKS if sinks_only else 0)))
+        return self.witness_rows()
+
+    def witness_rows(self) -> np.ndarray:
+        """nemo_fetch_witness: the rows of the last witness call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_witness(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, WITNESS_DTYPE)
+        self._chk(self.L.nemo_fetch_witness(self.h, _p(out), len(out), ctypes.byref(n)))
+        return out
+
+    def witness_mask(self, hyp: int, n_nodes: int) -> np.ndarray:
+        """nemo_fetch_witness_mask: one byte per node of hypothesis `hyp`'s graph (n_nodes of them), 1 = in W;
+        needs a call with masks=True."""
+        out = np.zeros(n_nodes, np.uint8)
+        self._chk(self.L.nemo_fetch_witness_mask(self.h, int(hyp), _p(out), len(out)))
+        return out
 
     def goal_labels(self, iteration: int, cond: int, d_out_ptr: int, cap: int) -> None:
         """nemo_goal_labels: [n, label...] of a run's goal labels into device memory."""
