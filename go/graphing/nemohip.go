@@ -873,6 +873,55 @@ func (n *Neo4J) MinCuts(iter uint, cond string, candidates []uint32, maxSize uin
 	return res, stats, nil
 }
 
+// LineageCuts returns all minimal cuts of at most maxSize (1..8) nodes of one
+// run's pre or post provenance among the candidates (nemo_lineage_cuts), as
+// MinCuts does up to size 3, by the search lineage-driven fault injection
+// makes: a fault set that does not defeat the outcome is extended only by the
+// candidates that lie in the derivation it leaves.  The cuts come sorted by
+// size, then by the colex order of their positions in the candidate list.  The
+// second result holds, per size 0..8, the sets evaluated and the minimal cuts
+// found (nemo_fetch_lineage_cut_stats).
+func (n *Neo4J) LineageCuts(iter uint, cond string, candidates []uint32, maxSize uint) ([]*MinCut, [18]uint64, error) {
+	var stats [18]uint64
+	var list *C.uint32_t
+	if candidates != nil {
+		nodes := make([]C.uint32_t, len(candidates)+1) // never empty: &nodes[0] below
+		for i, v := range candidates {
+			nodes[i] = C.uint32_t(v)
+		}
+		list = &nodes[0]
+	}
+	if err := n.err(C.nemo_lineage_cuts(n.ctx, C.uint32_t(iter), condIndex(cond), list, C.size_t(len(candidates)), C.uint32_t(maxSize), 0)); err != nil {
+		return nil, stats, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_lineage_cuts(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	cuts := make([]C.nemo_lineage_cut, cnt+1)
+	if err := n.err(C.nemo_fetch_lineage_cuts(n.ctx, &cuts[0], cnt, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	if err := n.err(C.nemo_fetch_lineage_cut_stats(n.ctx, (*C.uint64_t)(unsafe.Pointer(&stats[0])))); err != nil {
+		return nil, stats, err
+	}
+	p := n.graphs[2*n.runIdx[iter]+int(condIndex(cond))]
+	res := make([]*MinCut, cnt)
+	for k, cut := range cuts[:cnt] {
+		m := &MinCut{}
+		for j := 0; j < int(cut.size); j++ {
+			v := uint32(cut.node[j])
+			id, label := "", ""
+			if int(v) < len(p.goals) {
+				id, label = p.goals[v].ID, p.goals[v].Label
+			}
+			m.Nodes, m.IDs, m.Labels = append(m.Nodes, v), append(m.IDs, id), append(m.Labels, label)
+		}
+		res[k] = m
+	}
+	return res, stats, nil
+}
+
 // LabelKnockOut is the result of KnockoutLabels: one bit per (listed run, set).
 type LabelKnockOut struct {
 	Chunks int        // words per listed run: ceil(sets / 64)

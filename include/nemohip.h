@@ -280,7 +280,14 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       one workgroup per CU past 81920, the fastest of the three
  *                       points measured at the C3 shape; 0 = every graph in
  *                       device memory; -1 = the default); takes effect at the
- *                       next witness call; the grid cap is "kl_grid"'s            */
+ *                       next witness call; the grid cap is "kl_grid"'s;
+ *                       nemo_lineage_cuts takes its tier from the same option
+ *   "lineage_children_max"  most children one level of nemo_lineage_cuts may emit,
+ *                       counted before duplicates are removed (default 2^24 =
+ *                       16777216: 16 bytes per child gives 256 MiB, a memory bound,
+ *                       not a tuned number; at least 64, at most 2^31; -1 = the
+ *                       default); a level past it fails the call with
+ *                       NEMO_ERR_LIMIT                                            */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -622,6 +629,67 @@ int nemo_fetch_min_cuts(nemo_ctx *ctx, nemo_cut *out, uint64_t cap, uint64_t *n_
 /* Per size s = 1..3, out[3 (s - 1) ..]: live candidates entering the round,
  * hypotheses evaluated, minimal cuts found (zeros for s > max_size).           */
 int nemo_fetch_min_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
+
+/* ---- lineage-driven cut search: minimal cuts up to size 8 from surviving derivations ----
+ * The subject (a raw loaded graph g = 2r + cond), the candidates, dead_F(v), the
+ * roots, "the outcome is lost under F", "cut" and "minimal" are nemo_min_cuts'
+ * definitions above, unchanged.  cand == NULL means every sink goal of the graph
+ * in node-index order; candidates may be goals, rules or inner nodes.  A node
+ * >= V_g, or a node listed twice, is NEMO_ERR_INVALID, checked on the host before
+ * anything is uploaded.  max_size is 1..8 and flags 0; anything else is
+ * NEMO_ERR_INVALID ("max_size must be 1..8").  More than 65535 candidates is
+ * NEMO_ERR_LIMIT: a set is kept as eight u16 candidate positions.
+ * Result, whatever the search below does: all minimal cuts of size <= max_size
+ * among the candidates.  The rows are sorted by (size, colex order of the
+ * candidate positions): of two sets of one size the colex order compares the
+ * largest position first, then the next largest, and so on.  For size <= 3 this
+ * is nemo_min_cuts' row order (its live list keeps candidate order, so colex
+ * over live positions and colex over candidate positions agree).  A row's nodes
+ * ascend by candidate position, unused entries UINT32_MAX.
+ * Search (specified, so that the stats are deterministic): the hitting-set tree
+ * over surviving derivations, level by level.  Level 0 evaluates the empty set.
+ * Level d evaluates a frontier of distinct sets of size d; a set under which the
+ * outcome is lost is a minimal cut of size d and is not expanded.  For every
+ * other set F, W_F is nemo_witness_sets' single derivation under F (a needed goal
+ * needs its alive child of smallest node index; not NEMO_WIT_ALL), and the
+ * children of F are F + {e} for every candidate e that is in W_F.  The frontier
+ * of level d + 1 holds the distinct children of level d's non-cuts that have no
+ * proper subset among the cuts of sizes <= d.  The search stops after level
+ * max_size, or when a frontier is empty.  Every minimal cut is reached: a
+ * minimal cut C and a non-cut F inside it meet in W_F outside F (were no node of
+ * W_F in C, every node of W_F, an alive root among them, would be alive under C),
+ * so some child of F lies in C; a reached cut that is not minimal holds a smaller
+ * minimal cut found at an earlier level and was dropped before it was evaluated.
+ * Which events a level evaluates depends on the witnesses; the rows do not.
+ * n_cand == 0 with a list, a graph without roots, and a graph with no cut up to
+ * max_size give zero rows and NEMO_OK; in the first two cases no set is evaluated
+ * and every stat is 0.  An iteration that is not loaded is NEMO_ERR_NOTFOUND;
+ * cond outside 0 / 1 is NEMO_ERR_INVALID; a node context, and a call without a
+ * loaded corpus, return NEMO_ERR_STATE.
+ * Limits, NEMO_ERR_LIMIT, the call then leaves no results: a frontier of more
+ * than 2^32 - 2 sets; a level that emits more children (counted before duplicates
+ * are removed) than the option "lineage_children_max" allows (the message names
+ * the count and the option).  The emission buffer grows only: a level that
+ * counted more children than it holds runs again, once, behind a buffer of the
+ * counted size.
+ * The call blocks until the rows are on the host; per level two kernels run and
+ * one block of counters comes back (the cuts so far, the children counted, the
+ * next frontier's sets).  The results are the call's own state: valid until the
+ * next nemo_lineage_cuts or nemo_load_corpus (the fetches return NEMO_ERR_STATE
+ * otherwise), independent of every other call's state in both directions.  The
+ * tier is "wit_lds_max"'s (the image is the witness calls': the graph, the dead
+ * words and the need words), the grid cap "kl_grid"'s.                           */
+typedef struct nemo_lineage_cut {
+  uint32_t size;    /* 1..8                                                          */
+  uint32_t node[8]; /* nodes in candidate-list order, unused = UINT32_MAX            */
+} nemo_lineage_cut;
+int nemo_lineage_cuts(nemo_ctx *ctx, uint32_t iteration, int cond, const uint32_t *cand, size_t n_cand, uint32_t max_size,
+                      uint32_t flags);
+/* out[k] for every minimal cut k; out == NULL queries *n_out.                  */
+int nemo_fetch_lineage_cuts(nemo_ctx *ctx, nemo_lineage_cut *out, uint64_t cap, uint64_t *n_out);
+/* Per size d = 0..8: out[2 d] = sets evaluated at size d, out[2 d + 1] = minimal
+ * cuts found of size d (zeros past the last level the search reached).         */
+int nemo_fetch_lineage_cut_stats(nemo_ctx *ctx, uint64_t out[18]);
 
 /* ---- knock-out by label: fault sets tested against every listed run in one call ----
  * The subject (a raw loaded graph), dead_F(v), the roots and "the outcome is lost

@@ -363,6 +363,12 @@ int nemo_set_option(nemo_ctx *c, const char *name, int64_t value) {
     c->opt.wit_lds_max = wit::lds_max_option(value);
     return NEMO_OK;
   }
+  if (!strcmp(name, "lineage_children_max")) {  // most children a level of nemo_lineage_cuts may emit; -1: the default
+    const uint64_t v = lin::children_option(value);
+    if (!v) return fail(c, NEMO_ERR_INVALID, "lineage_children_max must be >= %llu (-1: the default, %llu)", LIN_CHILDREN_MIN, LIN_CHILDREN_DEFAULT);
+    c->opt.lin_children_max = v;
+    return NEMO_OK;
+  }
   if (!strcmp(name, "chains_comp_max")) {
     c->opt.comp_limit = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
     c->cs.dc.comp_limit = c->opt.comp_limit;

@@ -22,6 +22,7 @@
 #include "internal.h"
 #include "klabel_host.h"
 #include "lcut_host.h"
+#include "lin_host.h"
 #include "knock_host.h"
 #include "nearest_host.h"
 #include "node.h"
@@ -166,7 +167,8 @@ struct Options {
   uint32_t cut_grid = 0;                      // test knob: most workgroups of k_cut_lds / k_cut_glob (0: as many as are resident)
   bool kl_hitlist = true;                     // option kl_hitlist 0: k_kl_lds probes every node's label per chunk (the measured alternative)
   uint32_t kl_grid = 0;                       // test knob: most workgroups of k_kl_lds / k_kl_glob (0: as many as are resident)
-  uint32_t wit_lds_max = WIT_LDS_DEFAULT;     // largest LDS image (bytes) k_wit_lds takes (0: every graph to k_wit_glob)
+  uint32_t wit_lds_max = WIT_LDS_DEFAULT;     // largest LDS image (bytes) k_wit_lds / k_lin_lds take (0: every graph to k_wit_glob / k_lin_glob)
+  uint64_t lin_children_max = LIN_CHILDREN_DEFAULT;  // most children a level of nemo_lineage_cuts may emit (option lineage_children_max)
 };
 
 // Everything that belongs to the loaded corpus; release_corpus assigns CorpusState{}, so a member's
@@ -433,6 +435,28 @@ struct CorpusState : GraphSizes {
   DevBuf<uint64_t> d_wtneed;         // the kept need words (NEMO_WIT_MASKS)
   DevBuf<uint64_t> d_wtreg;          // the workgroups' regions: k_wit_glob's dead and need words, the hit list's rest
 
+  // lineage-driven cut search (k_lineage.hip): the call's own state, void after the next nemo_lineage_cuts or load;
+  // independent of every other call's state (kl_nlev above is the load's, not a result).  One group d_ln*, which grows
+  // only inside nemo_lineage_cuts, each buffer to the largest request so far, behind a wait for the stream: d_lndesc
+  // alone, before anything is counted; d_lncand, d_lnctr and d_lnreg together once the candidates are known, in this
+  // order; d_lnkids and d_lnktab, their contents dropped, and d_lnfront, its sets kept, when a level counted more
+  // children than the emission buffer holds; d_lncuts, its keys kept, and d_lnctab, filled again from them, before a
+  // level that could overfill them
+  bool lin_done = false;
+  uint64_t lin_stats[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size 0..8: sets evaluated, minimal cuts
+  std::vector<nemo_lineage_cut> lin_rows;  // the last call's rows, sorted
+  std::vector<uint32_t> lin_cand;    // the last call's candidates (nodes)
+  uint32_t lin_up[4] = {0, 0, 0, 0};  // the last call's uploads to d_lndesc
+  DevBuf<uint32_t> d_lndesc;         // [8] k_ko_leaves' list, offsets and counts for the one graph (cand == NULL)
+  DevBuf<uint32_t> d_lncand;         // [K] candidate position -> node
+  DevBuf<unsigned long long> d_lnctr;  // [4] cuts so far | children counted | the next frontier's sets | unused
+  DevBuf<uint64_t> d_lnreg;          // k_lin_glob: dead and need words of every workgroup of the launch
+  DevBuf<uint64_t> d_lnkids;         // [cap][2] the children a level emits
+  DevBuf<uint64_t> d_lnfront;        // [cap][2] the frontier
+  DevBuf<uint32_t> d_lnktab;         // the children's table: lin::table_slots(cap)
+  DevBuf<uint64_t> d_lncuts;         // [cap][2] the cuts found so far
+  DevBuf<uint32_t> d_lnctab;         // the cuts' table: lin::table_slots(cap)
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -525,12 +549,13 @@ struct nemo_ctx {
   hipEvent_t ev_lcuts = nullptr;   // nemo_min_label_cuts' level counts / round 1's words / totals / rows have reached pinned memory
   hipEvent_t ev_gcuts = nullptr;   // nemo_min_group_cuts' level counts / round 1's words / totals / rows have reached pinned memory
   hipEvent_t ev_wit = nullptr;     // the witness calls' level counts / rows have reached pinned memory
-  hipEvent_t *const events[25] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_lin = nullptr;     // nemo_lineage_cuts' counts / candidates / a level's counters / the cuts have reached pinned memory
+  hipEvent_t *const events[26] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
                                   &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts,
-                                  &ev_wit};
+                                  &ev_wit,     &ev_lin};
   // ... and the slices' (ev_state, ev_ready), destroyed with them
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
@@ -549,13 +574,14 @@ struct nemo_ctx {
   Pinned<uint32_t> h_lcuts;  // nemo_min_label_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
   Pinned<uint32_t> h_gcuts;  // nemo_min_group_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
   Pinned<uint32_t> h_wit;    // the witness calls: the level counts; then the rows
-  void **const pinned[28] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint64_t> h_lin;    // nemo_lineage_cuts: the level counts, the counts and candidates, a level's counters; then the cuts' keys
+  void **const pinned[29] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
                              h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot(),
-                             h_gcuts.slot(),  h_wit.slot()};
+                             h_gcuts.slot(),  h_wit.slot(),    h_lin.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

@@ -325,6 +325,41 @@ uint32_t wit_lds_resident(uint32_t lds_bytes, uint32_t n_cu);
 void launch_wit_lds(const DevCorpus &c, const WitArgs &a, uint32_t grid, hipStream_t s);  // a.lds_total bytes of LDS
 void launch_wit_glob(const DevCorpus &c, const WitArgs &a, uint32_t grid, hipStream_t s);
 
+// One level of nemo_lineage_cuts (k_lineage.hip): the frontier's sets, 64 per chunk, are evaluated on the one graph
+// (k_lin_lds / k_lin_glob), which appends the lost ones to the cuts and emits the children of the others; k_lin_filter
+// makes the next frontier of the children.  A set is a key of two u64 (lin_host.h).
+struct LinArgs {
+  uint32_t graph;            // 2r + cond
+  const uint32_t *cand;      // [K] candidate position -> node
+  uint32_t K;
+  const uint64_t *front;     // [n_front][2] the level's sets
+  uint32_t n_front, n_chunks;
+  uint32_t emit;             // 0: the last level, no children; 1: emit them
+  uint32_t redo;             // 1: the level runs again behind a grown emission buffer: its cuts are in place
+  uint64_t *kids;            // [kids_cap][2] the emitted children
+  uint64_t kids_cap;
+  uint64_t *cuts;            // [...][2] the cuts found so far, this level's behind them
+  uint32_t *ctab;            // [cslots] the cuts' table: index + 1, 0 = empty
+  uint64_t cslots;
+  unsigned long long *ctr;   // [0] cuts so far | [1] children counted (not capped) | [2] the next frontier's sets
+  uint32_t lds_total;        // k_lin_lds: the launch's dynamic LDS
+  uint64_t *region;          // k_lin_glob: [workgroups][region_words] dead words, then need words
+  uint64_t region_words;
+  // k_lin_filter
+  uint32_t *ktab;            // [kslots] the children's table, zero
+  uint64_t kslots;
+  uint64_t *next;            // [...][2] the next frontier (as many sets as kids_cap)
+  uint32_t cut_sizes;        // bit s: a cut of size s was found at an earlier level
+  uint32_t size;             // the level: the sets' size
+  uint64_t cuts_before;      // cuts before this level
+};
+uint32_t lin_lds_resident(uint32_t lds_bytes, uint32_t n_cu);
+void launch_lin_lds(const DevCorpus &c, const LinArgs &a, uint32_t grid, hipStream_t s);  // a.lds_total bytes of LDS
+void launch_lin_glob(const DevCorpus &c, const LinArgs &a, uint32_t grid, hipStream_t s);
+void launch_lin_filter(const LinArgs &a, uint32_t grid, hipStream_t s);
+// the cuts [0, n) into a zeroed table (behind a grown list)
+void launch_lin_rehash(const LinArgs &a, uint64_t n, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

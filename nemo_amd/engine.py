@@ -53,6 +53,8 @@ GROUP_CUT_DTYPE = np.dtype([("size", np.uint32), ("group", np.uint32, (3,))])
 WITNESS_DTYPE = np.dtype([("graph", np.uint32), ("n_roots", np.uint32), ("roots_alive", np.uint32), ("n_nodes", np.uint32),
                           ("n_sinks", np.uint32)])
 WIT_ALL, WIT_MASKS, WIT_SINKS = 1, 2, 4  # NEMO_WIT_ALL, NEMO_WIT_MASKS, NEMO_WIT_SINKS
+# struct nemo_lineage_cut (nemo_fetch_lineage_cuts)
+LINEAGE_CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (8,))])
 
 
 def header_symbols() -> List[str]:
@@ -131,6 +133,9 @@ def lib():
             "nemo_min_cuts": ([vp, u32, i32, vp, sz, u32, u32], i32),
             "nemo_fetch_min_cuts": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_min_cut_stats": ([vp, vp], i32),
+            "nemo_lineage_cuts": ([vp, u32, i32, vp, sz, u32, u32], i32),
+            "nemo_fetch_lineage_cuts": ([vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_lineage_cut_stats": ([vp, vp], i32),
             "nemo_knockout_labels": ([vp, vp, sz, i32, vp, vp, sz, u32], i32),
             "nemo_fetch_knockout_labels": ([vp, vp, vp, u64], i32),
             "nemo_fetch_knockout_label_counts": ([vp, vp, vp, u64], i32),
@@ -502,6 +507,35 @@ class Engine:
         out = np.zeros(9, np.uint64)
         self._chk(self.L.nemo_fetch_min_cut_stats(self.h, _p(out)))
         return out.reshape(3, 3)
+
+    def lineage_cuts(self, iteration: int, cond: int, candidates: Optional[Sequence[int]] = None, max_size: int = 3) -> np.ndarray:
+        """nemo_lineage_cuts: all minimal cuts of size <= max_size (1..8) of a run's pre (cond 0) or post (cond 1) graph
+        among `candidates` (as min_cuts takes them; at most 65535), found by the lineage-driven search: a fault set
+        that is no cut is extended only by candidates that lie in the derivation it leaves.  Returns the rows as a
+        structured array (LINEAGE_CUT_DTYPE: size, node[8] ascending by candidate position, unused entries UINT32_MAX),
+        sorted by (size, colex order of the candidate positions); lineage_cut_stats() has the levels' counts."""
+        if candidates is None:
+            self._chk(self.L.nemo_lineage_cuts(self.h, int(iteration), int(cond), None, 0, int(max_size), 0))
+        else:
+            cand = np.ascontiguousarray(candidates, dtype=np.uint32)
+            keep = cand if len(cand) else np.zeros(1, np.uint32)  # an empty list is a list: never NULL
+            self._chk(self.L.nemo_lineage_cuts(self.h, int(iteration), int(cond), _p(keep), len(cand), int(max_size), 0))
+        return self.lineage_cut_rows()
+
+    def lineage_cut_rows(self) -> np.ndarray:
+        """nemo_fetch_lineage_cuts: the rows of the last lineage_cuts call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_lineage_cuts(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, LINEAGE_CUT_DTYPE)
+        self._chk(self.L.nemo_fetch_lineage_cuts(self.h, _p(out), len(out), ctypes.byref(n)))
+        return out
+
+    def lineage_cut_stats(self) -> np.ndarray:
+        """nemo_fetch_lineage_cut_stats: a 9 x 2 u64 array, row d = (sets evaluated at size d, minimal cuts found of
+        size d), d = 0..8."""
+        out = np.zeros(18, np.uint64)
+        self._chk(self.L.nemo_fetch_lineage_cut_stats(self.h, _p(out)))
+        return out.reshape(9, 2)
 
     def knockout_labels(self, iters: Sequence[int], cond: int, sets, sinks_only: bool = False):
         """nemo_knockout_labels: hypotheses that name interned labels, tested on every listed run's pre (cond 0) or
