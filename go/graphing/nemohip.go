@@ -1101,6 +1101,59 @@ func (n *Neo4J) MinGroupCuts(iters []uint, cond string, groups [][]uint32, maxSi
 	return res, stats, nil
 }
 
+// LineageGroupCuts answers MinGroupCuts' question for sets of up to eight fault
+// events (nemo_lineage_group_cuts): every minimal set of at most maxSize (1..8)
+// of the groups whose loss together defeats the outcome on at least minRuns of
+// the listed runs' pre or post provenance (0: on every one of them).  It
+// searches the way LineageCuts does: a set that is no cut is extended only by
+// events that a surviving derivation of some listed run rests on.  The cuts
+// come sorted by size, then by the colex order of their positions in the group
+// list; up to size 3 they are MinGroupCuts' own.  The second result holds, per
+// size 0..8, the sets evaluated and the minimal cuts found.
+func (n *Neo4J) LineageGroupCuts(iters []uint, cond string, groups [][]uint32, maxSize uint, minRuns uint, sinksOnly bool) ([]*GroupCut, [18]uint64, error) {
+	var stats [18]uint64
+	its := make([]C.uint32_t, len(iters)+1)
+	for i, it := range iters {
+		its[i] = C.uint32_t(it)
+	}
+	off := make([]C.uint64_t, len(groups)+1)
+	var labels []C.uint32_t
+	for k, group := range groups {
+		for _, l := range group {
+			labels = append(labels, C.uint32_t(l))
+		}
+		off[k+1] = C.uint64_t(len(labels))
+	}
+	labels = append(labels, 0) // never empty: &labels[0] below
+	var flags C.uint32_t
+	if sinksOnly {
+		flags = C.NEMO_KL_SINKS
+	}
+	if err := n.err(C.nemo_lineage_group_cuts(n.ctx, &its[0], C.size_t(len(iters)), condIndex(cond), &off[0], &labels[0], C.size_t(len(groups)), C.uint32_t(maxSize), C.uint32_t(minRuns), flags)); err != nil {
+		return nil, stats, err
+	}
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_lineage_group_cuts(n.ctx, nil, nil, 0, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	rows, nLost := make([]C.nemo_lineage_group_cut, cnt+1), make([]C.uint32_t, cnt+1)
+	if err := n.err(C.nemo_fetch_lineage_group_cuts(n.ctx, &rows[0], &nLost[0], cnt, &cnt)); err != nil {
+		return nil, stats, err
+	}
+	if err := n.err(C.nemo_fetch_lineage_group_cut_stats(n.ctx, (*C.uint64_t)(unsafe.Pointer(&stats[0])))); err != nil {
+		return nil, stats, err
+	}
+	res := make([]*GroupCut, cnt)
+	for k, gc := range rows[:cnt] {
+		m := &GroupCut{NLost: uint32(nLost[k])}
+		for j := 0; j < int(gc.size); j++ {
+			m.Groups = append(m.Groups, uint32(gc.group[j]))
+		}
+		res[k] = m
+	}
+	return res, stats, nil
+}
+
 // Witness is the surviving derivation of one graph under one fault hypothesis:
 // what is left of the outcome's provenance, and what it rests on.
 type Witness struct {

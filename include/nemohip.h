@@ -869,6 +869,90 @@ int nemo_fetch_min_group_cuts(nemo_ctx *ctx, nemo_group_cut *out, uint32_t *n_lo
  * candidates entering the round, hypotheses evaluated, minimal cuts found.     */
 int nemo_fetch_min_group_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
 
+/* ---- lineage cut search over fault events: minimal cuts up to size 8 across runs ----
+ * nemo_min_group_cuts' question, answered by nemo_lineage_cuts' search: which
+ * fault events, lost together, defeat the outcome on at least q of the listed
+ * runs, for sets of up to eight events.
+ * Definitions: the candidates (candidate k is the label set G_k), F(i,S),
+ * NEMO_KL_SINKS, lost_count(S), q = min_runs (0 means n), "cut" and minimality
+ * over candidate positions are nemo_min_group_cuts' definitions above,
+ * unchanged; so is what counts as legal input: empty, nested and overlapping
+ * groups, a label named twice, a label no listed node carries, a run listed
+ * twice (it counts twice).
+ * Result, whatever the search below does: all minimal cuts of size <= max_size
+ * (1..8), sorted by (size, colex order of the candidate positions: the largest
+ * position first, then the next largest); a row's positions ascend, unused
+ * entries UINT32_MAX; n_lost[k] is row k's lost_count.  For max_size <= 3 the
+ * rows and n_lost are nemo_min_group_cuts' own, in its order: a minimal cut
+ * holds live candidates only (a candidate that hits no listed node changes no
+ * F(i,S), and one that is a cut alone is a row by itself), the sets of live
+ * candidates it evaluates are all of them, and its live list keeps candidate
+ * order, so colex over live positions and colex over candidate positions agree.
+ * Search (specified, so that the stats are deterministic): level 0 evaluates the
+ * empty set; level d evaluates a frontier of distinct sets of size d on every
+ * list position.  A set with lost_count >= q is a minimal cut of size d and is
+ * not expanded.  For every other set F the children are F + {k}: candidate k
+ * qualifies when, for some list position i on which the outcome is not lost
+ * under F(i,F), some label of G_k is the label of a node of W_F^i, where W_F^i
+ * is nemo_witness_labels' single derivation on that graph under F(i,F) (a needed
+ * goal needs its alive child of smallest node index; not NEMO_WIT_ALL).  Under
+ * NEMO_KL_SINKS only sink goals of W_F^i count.  The frontier of level d + 1
+ * holds the distinct children that have no proper subset among the cuts of sizes
+ * <= d.  The search stops after level max_size or at an empty frontier.
+ * Every minimal cut is reached.  Take a minimal cut C and a non-cut F inside it:
+ * lost_count(F) < q <= lost_count(C) and lost is monotone, so there is a list
+ * position i that is lost under C and not under F.  F(i,C) must hit a node v of
+ * W_F^i: otherwise every node of W_F^i, an alive root among them, would stay
+ * alive under C.  v is alive under F, so the candidate of C whose group names
+ * v's label is not in F; hence a child of F lies in C.  A reached cut that is
+ * not minimal holds an earlier minimal cut and was filtered before it was
+ * evaluated.
+ * Emission: children are emitted from every (list position, set) on which the
+ * set is not lost, whether or not the cross-run count later makes the set a
+ * cut: the children of a set that turns out to be a cut are supersets of it and
+ * the subset filter drops them.  This keeps a level's evaluation one fused pass
+ * and costs nothing under q = n, where a cut is lost on every list position and
+ * emits nothing.  The child count that the emission limit is checked against is
+ * this count: every list position's children, before duplicates are removed.
+ * NEMO_ERR_INVALID, all checked on the host before anything is uploaded: a
+ * decreasing group_off (the message gives the group); a label equal to
+ * UINT32_MAX (the message gives the group and the position in group_labels);
+ * iters == NULL with n > 0, group_off == NULL with n_groups > 0, group_labels
+ * == NULL where the groups name a label; max_size outside 1..8 ("max_size must
+ * be 1..8"); min_runs > n; cond outside 0 / 1; unknown flags.  NEMO_ERR_LIMIT:
+ * more than 65535 groups (a set is kept as eight u16 candidate positions);
+ * nemo_min_group_cuts' label-count limits (2^32 - 1 labels in all, 2^24 in one
+ * group, D + 1 + V <= 2^32 - 1); a level with n * ceil(frontier / 64) > 2^28 lost
+ * words; a frontier of more than 2^32 - 2 sets; a level whose counted children
+ * pass the option "lineage_children_max" (the message names the count and the
+ * option).  A call that ends in a limit leaves no results.  The emission buffer
+ * grows only: a level that counted more children than it holds runs again,
+ * once, behind a buffer of the counted size, and does not append its cuts twice.
+ * n == 0, n_groups == 0, or every listed graph empty: zero rows, every stat 0,
+ * NEMO_OK, and nothing is evaluated.  An iteration that is not loaded is
+ * NEMO_ERR_NOTFOUND; a node context, and a call without a loaded corpus, return
+ * NEMO_ERR_STATE.
+ * The call blocks until the rows are on the host; per level three kernels run
+ * (the evaluation once per tier) and one block of counters comes back.  The
+ * results are the call's own state: valid until the next
+ * nemo_lineage_group_cuts or nemo_load_corpus (the fetches return
+ * NEMO_ERR_STATE otherwise), independent of every other call's state in both
+ * directions.  No option of its own: the tier is "wit_lds_max"'s, the grid cap
+ * "kl_grid"'s, the emission limit "lineage_children_max"'s.                     */
+typedef struct nemo_lineage_group_cut {
+  uint32_t size;     /* 1..8                                                         */
+  uint32_t group[8]; /* candidate positions, ascending, unused = UINT32_MAX          */
+} nemo_lineage_group_cut;
+int nemo_lineage_group_cuts(nemo_ctx *ctx, const uint32_t *iters, size_t n, int cond,
+                            const uint64_t *group_off /* [n_groups + 1] */, const uint32_t *group_labels,
+                            size_t n_groups, uint32_t max_size, uint32_t min_runs, uint32_t flags);
+/* out[k] for every minimal cut k, n_lost[k] its lost_count (n_lost may be NULL);
+ * out == NULL queries *n_out.                                                  */
+int nemo_fetch_lineage_group_cuts(nemo_ctx *ctx, nemo_lineage_group_cut *out, uint32_t *n_lost, uint64_t cap, uint64_t *n_out);
+/* As nemo_fetch_lineage_cut_stats: per size d = 0..8, out[2 d] = sets evaluated
+ * at size d, out[2 d + 1] = minimal cuts found of size d.                      */
+int nemo_fetch_lineage_group_cut_stats(nemo_ctx *ctx, uint64_t out[18]);
+
 /* ---- surviving derivations: why a run's outcome withstands a fault set ---------
  * The other half of the knock-out family: where those calls say whether a fault
  * set defeats the outcome, these say which derivation is left when it does not,

@@ -7,28 +7,6 @@
 
 namespace {
 
-// b to `need` elements with its first `keep` elements kept (the frontier behind a grown emission buffer, the cuts
-// before a level that could overfill them): a new block, a copy on the stream, a wait, the old block released
-template <class T>
-int grow_keep(nemo_ctx *c, DevBuf<T> &b, uint64_t need, uint64_t keep) {
-  if (b.p && need <= b.cap) return NEMO_OK;
-  DevBuf<T> nb;
-  if (int rc = nb.grow(c, need)) return rc;
-  if (keep && b.p) HIPCHK(c, hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  b.release(c);
-  b = nb;
-  return NEMO_OK;
-}
-
-// b to `need` elements, its contents dropped, behind a wait for the stream (an earlier launch may still read it)
-template <class T>
-int grow_drop(nemo_ctx *c, DevBuf<T> &b, uint64_t need) {
-  if (b.p && need <= b.cap) return NEMO_OK;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return b.grow(c, need);
-}
-
 int lin_empty(CorpusState &cs) {  // zero rows, every stat 0
   cs.lin_done = true;
   return NEMO_OK;

@@ -24,6 +24,7 @@
 #include "lcut_host.h"
 #include "lin_host.h"
 #include "knock_host.h"
+#include "lgc_host.h"
 #include "nearest_host.h"
 #include "node.h"
 #include "pairs_host.h"
@@ -457,6 +458,34 @@ struct CorpusState : GraphSizes {
   DevBuf<uint64_t> d_lncuts;         // [cap][2] the cuts found so far
   DevBuf<uint32_t> d_lnctab;         // the cuts' table: lin::table_slots(cap)
 
+  // lineage cut search over fault events (k_lgcuts.hip): the call's own state, void after the next
+  // nemo_lineage_group_cuts or load; independent of every other call's state (kl_nlev above is the load's, not a
+  // result).  One group d_lg*, which grows only inside nemo_lineage_group_cuts, each buffer to the largest request so
+  // far, behind a wait for the stream: the first seven together once the call is checked, in this order; d_lglost
+  // alone before a level of more chunks; d_lgkids and d_lgktab, their contents dropped, and d_lgfront, its sets kept,
+  // when a level counted more children than the emission buffer holds; d_lgcuts and d_lgnl, their contents kept, and
+  // d_lgctab, filled again from the keys, before a level that could overfill them
+  bool lg_done = false;
+  uint64_t lg_stats[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size 0..8: sets evaluated, minimal cuts
+  std::vector<nemo_lineage_group_cut> lg_rows;  // the last call's rows, sorted,
+  std::vector<uint32_t> lg_nlost;    // ... and their lost counts
+  std::vector<uint32_t> lg_desc;     // the last call's uploads: [n] graphs | the LDS tier's list positions | the global tier's,
+  std::vector<uint32_t> lg_off;      // ... [K + 1] the groups' offsets from the first group's
+  DevBuf<uint32_t> d_lgoff;          // [K + 1]
+  DevBuf<uint32_t> d_lggrow;         // the groups' labels, rewritten as rows
+  DevBuf<uint32_t> d_lgkey;          // the table's keys; then the rows handed out (one word)
+  DevBuf<uint32_t> d_lgval;          // ... and rows
+  DevBuf<uint32_t> d_lgdesc;         // [2 n]
+  DevBuf<unsigned long long> d_lgctr;  // [4] cuts so far | children counted | the next frontier's sets | unused
+  DevBuf<uint64_t> d_lgreg;          // the workgroups' regions: k_lgc_glob's dead and need words, the rows' need words, the hit list's rest
+  DevBuf<uint64_t> d_lglost;         // [n][chunks] a level's lost words
+  DevBuf<uint64_t> d_lgkids;         // [cap][2] the children a level emits
+  DevBuf<uint64_t> d_lgfront;        // [cap][2] the frontier
+  DevBuf<uint32_t> d_lgktab;         // the children's table: lin::table_slots(cap)
+  DevBuf<uint64_t> d_lgcuts;         // [cap][2] the cuts found so far
+  DevBuf<uint32_t> d_lgnl;           // [cap] their lost counts
+  DevBuf<uint32_t> d_lgctab;         // the cuts' table: lin::table_slots(cap)
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -550,12 +579,13 @@ struct nemo_ctx {
   hipEvent_t ev_gcuts = nullptr;   // nemo_min_group_cuts' level counts / round 1's words / totals / rows have reached pinned memory
   hipEvent_t ev_wit = nullptr;     // the witness calls' level counts / rows have reached pinned memory
   hipEvent_t ev_lin = nullptr;     // nemo_lineage_cuts' counts / candidates / a level's counters / the cuts have reached pinned memory
-  hipEvent_t *const events[26] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_lgc = nullptr;     // nemo_lineage_group_cuts' level counts / a level's counters / the cuts have reached pinned memory
+  hipEvent_t *const events[27] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
                                   &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts,
-                                  &ev_wit,     &ev_lin};
+                                  &ev_wit,     &ev_lin,     &ev_lgc};
   // ... and the slices' (ev_state, ev_ready), destroyed with them
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
@@ -575,13 +605,14 @@ struct nemo_ctx {
   Pinned<uint32_t> h_gcuts;  // nemo_min_group_cuts: the level counts, round 1's words, the totals; then the rows and their n_lost
   Pinned<uint32_t> h_wit;    // the witness calls: the level counts; then the rows
   Pinned<uint64_t> h_lin;    // nemo_lineage_cuts: the level counts, the counts and candidates, a level's counters; then the cuts' keys
-  void **const pinned[29] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint64_t> h_lgc;    // nemo_lineage_group_cuts: the level counts, a level's counters; then the cuts' keys and lost counts
+  void **const pinned[30] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
                              h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot(),
-                             h_gcuts.slot(),  h_wit.slot(),    h_lin.slot()};
+                             h_gcuts.slot(),  h_wit.slot(),    h_lin.slot(),   h_lgc.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

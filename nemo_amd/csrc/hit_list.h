@@ -1,4 +1,4 @@
-// hit_list.h — a graph's hit list as k_lcuts.hip and k_gcuts.hip keep it: the graph's nodes grouped by a row id
+// hit_list.h — a graph's hit list as k_lcuts.hip, k_gcuts.hip, k_witness.hip and k_lgcuts.hip keep it: the graph's nodes grouped by a row id
 // (k_lc_*: the live position of the node's label; k_gc_*: the distinct label itself), k1 rows, u32 entries:
 // [0 .. k1] the rows' offsets, then the rows' nodes.  The first `cap` entries live in LDS behind the image, the
 // others in the workgroup's region (lcut_host.h: list_entries, region_words).

@@ -360,6 +360,33 @@ void launch_lin_filter(const LinArgs &a, uint32_t grid, hipStream_t s);
 // the cuts [0, n) into a zeroed table (behind a grown list)
 void launch_lin_rehash(const LinArgs &a, uint64_t n, hipStream_t s);
 
+// One level of nemo_lineage_group_cuts (k_lgcuts.hip): the frontier's sets of candidate positions, 64 per chunk, are
+// evaluated on every listed graph (k_lgc_lds / k_lgc_glob: a lost word per (list position, chunk), the children of the
+// sets that are not lost); k_lgc_cuts counts a set's lost bits down the list positions and appends the cuts;
+// k_lin_filter (on `l`) makes the next frontier.  `l` is the level as nemo_lineage_cuts' kernels read it: of its
+// fields the evaluation leaves graph, cand and redo alone; l.K is the number of groups.
+struct LgcArgs {
+  LinArgs l;
+  const uint32_t *goff;      // [K + 1] candidate position -> its first entry in grow
+  const uint32_t *grow;      // the groups' labels as rows of the n_dist distinct labels (k_gc_table / k_gc_rows)
+  uint32_t n_dist;
+  const uint32_t *key, *val; // [slots] the table label + 1 -> row (klabel_host.h's hash)
+  uint64_t slots;
+  const uint32_t *graph;     // [n] list position -> graph
+  const uint32_t *pos;       // [n_tier] the launched tier's list positions
+  uint32_t n_tier;           // list positions of the launched tier
+  uint32_t parts;            // chunk ranges per graph (klabel::split)
+  uint32_t sinks;            // 1: only sink goals match a label (NEMO_KL_SINKS)
+  uint64_t glob_words;       // k_lgc_glob: dead words, then need words at the region's start
+  uint64_t *lost;            // [n][n_chunks] the level's lost words
+  uint32_t n, q;             // list positions of the call; a cut is lost on at least q of them
+  uint32_t *n_lost;          // k_lgc_cuts: [...] lost_count of each cut, beside l.cuts
+};
+uint32_t lgc_lds_resident(uint32_t lds_bytes, uint32_t n_cu);
+void launch_lgc_lds(const DevCorpus &c, const LgcArgs &a, uint32_t grid, hipStream_t s);  // a.l.lds_total bytes of LDS
+void launch_lgc_glob(const DevCorpus &c, const LgcArgs &a, uint32_t grid, hipStream_t s);
+void launch_lgc_cuts(const LgcArgs &a, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

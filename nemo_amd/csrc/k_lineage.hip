@@ -12,6 +12,7 @@
 #include "device.h"
 #include "internal.h"
 #include "ko_sweep.h"
+#include "lin_dev.h"
 #include "lin_host.h"
 #include "wit_down.h"
 #include "wit_host.h"
@@ -19,33 +20,6 @@
 namespace nemo {
 
 static_assert(LIN_BLOCK == KO_BLOCK, "lin_host.h sizes k_lin_filter's grid by KO_BLOCK threads");
-
-__device__ __forceinline__ lin::Key lin_load(const uint64_t *keys, uint64_t i) {
-  const ulonglong2 k = *reinterpret_cast<const ulonglong2 *>(keys + 2ull * i);
-  return lin::Key{k.x, k.y};
-}
-__device__ __forceinline__ void lin_store(uint64_t *keys, uint64_t i, const lin::Key &k) {
-  *reinterpret_cast<ulonglong2 *>(keys + 2ull * i) = make_ulonglong2(k.lo, k.hi);
-}
-
-// the wave's exclusive prefix of n and, in every lane, the wave's sum
-__device__ __forceinline__ uint32_t lin_wave_scan(uint32_t n, uint32_t *total) {
-  const uint32_t lane = lane_id();
-  uint32_t incl = n;
-#pragma unroll
-  for (int dd = 1; dd < 64; dd <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)incl, dd);
-    if ((int)lane >= dd) incl += y;
-  }
-  *total = (uint32_t)__shfl((int)incl, 63);
-  return incl - n;
-}
-
-// cut i (its key is in a.cuts) into the cuts' table: the cuts are distinct sets, so a taken slot is another's
-__device__ __forceinline__ void lin_cut_insert(const LinArgs &a, uint32_t i, const lin::Key &k) {
-  uint64_t h = lin::first_slot(k, a.cslots);
-  while (atomicCAS(&a.ctab[h], 0u, i + 1u) != 0u) h = lin::next_slot(h, a.cslots);  // ends: at most half of the slots are taken
-}
 
 // One chunk ci of the frontier on the staged graph.  Ends behind a barrier.  All 256 threads.
 template <bool LDS>

@@ -17,6 +17,29 @@ static inline int wait_copied(nemo_ctx *c, hipEvent_t ev) {
   return NEMO_OK;
 }
 
+// ---- a buffer that grows alone inside a call (nemo_lineage_cuts, nemo_lineage_group_cuts) ------------------
+// b to `need` elements with its first `keep` elements kept (the frontier behind a grown emission buffer, the cuts
+// before a level that could overfill them): a new block, a copy on the stream, a wait, the old block released
+template <class T>
+static int grow_keep(nemo_ctx *c, DevBuf<T> &b, uint64_t need, uint64_t keep) {
+  if (b.p && need <= b.cap) return NEMO_OK;
+  DevBuf<T> nb;
+  if (int rc = nb.grow(c, need)) return rc;
+  if (keep && b.p) HIPCHK(c, hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  b.release(c);
+  b = nb;
+  return NEMO_OK;
+}
+
+// b to `need` elements, its contents dropped, behind a wait for the stream (an earlier launch may still read it)
+template <class T>
+static int grow_drop(nemo_ctx *c, DevBuf<T> &b, uint64_t need) {
+  if (b.p && need <= b.cap) return NEMO_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return b.grow(c, need);
+}
+
 // What a workgroup of k_kl_lds / k_lc_lds takes of a CU's LDS beside its dynamic part: the kernel's static LDS (80
 // and 48 bytes by the compiler's report, profiles/r17_kernel_resources.txt), rounded up to whole allocation granules
 // with one to spare.  A value too small cannot cost a resident workgroup: ko_lds_total's second query refuses the

@@ -1,5 +1,5 @@
 // wit_down.h — the top-down need pass of the surviving derivations, shared by k_witness.hip (nemo_witness_sets /
-// nemo_witness_labels) and k_lineage.hip (nemo_lineage_cuts), in the manner of ko_sweep.h and diff_walk.h: how a need
+// nemo_witness_labels), k_lineage.hip (nemo_lineage_cuts) and k_lgcuts.hip (nemo_lineage_group_cuts), in the manner of ko_sweep.h and diff_walk.h: how a need
 // word is read and ORed on either tier, and the pass itself over a swept chunk (DESIGN.md §Surviving derivations).
 #pragma once
 #include "device.h"

@@ -55,6 +55,8 @@ WITNESS_DTYPE = np.dtype([("graph", np.uint32), ("n_roots", np.uint32), ("roots_
 WIT_ALL, WIT_MASKS, WIT_SINKS = 1, 2, 4  # NEMO_WIT_ALL, NEMO_WIT_MASKS, NEMO_WIT_SINKS
 # struct nemo_lineage_cut (nemo_fetch_lineage_cuts)
 LINEAGE_CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (8,))])
+# struct nemo_lineage_group_cut (nemo_fetch_lineage_group_cuts)
+LINEAGE_GROUP_CUT_DTYPE = np.dtype([("size", np.uint32), ("group", np.uint32, (8,))])
 
 
 def header_symbols() -> List[str]:
@@ -145,6 +147,9 @@ def lib():
             "nemo_min_group_cuts": ([vp, vp, sz, i32, vp, vp, sz, u32, u32, u32], i32),
             "nemo_fetch_min_group_cuts": ([vp, vp, vp, u64, P(u64)], i32),
             "nemo_fetch_min_group_cut_stats": ([vp, vp], i32),
+            "nemo_lineage_group_cuts": ([vp, vp, sz, i32, vp, vp, sz, u32, u32, u32], i32),
+            "nemo_fetch_lineage_group_cuts": ([vp, vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_lineage_group_cut_stats": ([vp, vp], i32),
             "nemo_witness_sets": ([vp, u32, i32, vp, vp, sz, u32], i32),
             "nemo_witness_labels": ([vp, vp, sz, i32, vp, vp, sz, u32], i32),
             "nemo_fetch_witness": ([vp, vp, u64, P(u64)], i32),
@@ -640,6 +645,46 @@ class Engine:
         out = np.zeros(9, np.uint64)
         self._chk(self.L.nemo_fetch_min_group_cut_stats(self.h, _p(out)))
         return out.reshape(3, 3)
+
+    def lineage_group_cuts(self, iters: Sequence[int], cond: int, groups, max_size: int = 3, min_runs: int = 0,
+                           sinks_only: bool = False):
+        """nemo_lineage_group_cuts: min_group_cuts' question for sets of up to eight fault events, answered by the
+        lineage-driven search: all minimal sets of <= max_size (1..8) candidates whose loss together defeats the
+        outcome on at least min_runs of the listed runs' pre (cond 0) or post (cond 1) graphs (0: on every list
+        position); a set that is no cut is extended only by events that some surviving derivation rests on.  groups:
+        as min_group_cuts takes them (at most 65535).  Returns (rows, n_lost): rows a structured array
+        (LINEAGE_GROUP_CUT_DTYPE: size, group[8] the candidate positions, ascending, unused entries UINT32_MAX) sorted
+        by (size, colex order of the candidate positions), n_lost[k] the list positions on which row k is lost;
+        lineage_group_cut_stats() has the levels' counts."""
+        if isinstance(groups, tuple) and len(groups) == 2 and isinstance(groups[0], np.ndarray):
+            off = np.ascontiguousarray(groups[0], dtype=np.uint64)
+            labels = np.ascontiguousarray(groups[1], dtype=np.uint32)
+            n_groups = max(len(off) - 1, 0)
+        else:
+            n_groups = len(groups)
+            off = np.zeros(n_groups + 1, np.uint64)
+            off[1:] = np.cumsum([len(x) for x in groups], dtype=np.uint64)
+            labels = np.ascontiguousarray([v for x in groups for v in x], dtype=np.uint32)
+        it = np.ascontiguousarray(iters, dtype=np.uint32)
+        keep = labels if len(labels) else np.zeros(1, np.uint32)  # an empty list is a list: never NULL
+        self._chk(self.L.nemo_lineage_group_cuts(self.h, _p(it), len(it), int(cond), off.ctypes.data, _p(keep), n_groups,
+                                                 int(max_size), int(min_runs), KL_SINKS if sinks_only else 0))
+        return self.lineage_group_cut_rows()
+
+    def lineage_group_cut_rows(self):
+        """nemo_fetch_lineage_group_cuts: (rows, n_lost) of the last lineage_group_cuts call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_lineage_group_cuts(self.h, None, None, 0, ctypes.byref(n)))
+        out, n_lost = np.zeros(n.value, LINEAGE_GROUP_CUT_DTYPE), np.zeros(n.value, np.uint32)
+        self._chk(self.L.nemo_fetch_lineage_group_cuts(self.h, _p(out), _p(n_lost), len(out), ctypes.byref(n)))
+        return out, n_lost
+
+    def lineage_group_cut_stats(self) -> np.ndarray:
+        """nemo_fetch_lineage_group_cut_stats: a 9 x 2 u64 array, row d = (sets evaluated at size d, minimal cuts found
+        of size d), d = 0..8."""
+        out = np.zeros(18, np.uint64)
+        self._chk(self.L.nemo_fetch_lineage_group_cut_stats(self.h, _p(out)))
+        return out.reshape(9, 2)
 
     def witness_sets(self, iteration: int, cond: int, sets: Sequence[Sequence[int]], all: bool = False, masks: bool = False) -> np.ndarray:
         """nemo_witness_sets: the surviving derivation of one graph under explicit hypotheses, each a set of local
