@@ -1,11 +1,12 @@
 // api_lgcuts.hip — nemo_lineage_group_cuts and its fetches (k_lgcuts.hip, lgc_host.h; DESIGN.md §Lineage cut search
 // over fault events).  The checks of the groups are nemo_min_group_cuts' (gcut_host.h), the label -> row table its
 // kernels', the tier rule and image the witness calls' (wit_host.h), the keys, the tables, the filter and the level
-// loop nemo_lineage_cuts' (lin_host.h, k_lineage.hip).  The host drives the levels: per level it queues the evaluation
-// on either tier, the cross-run count and the filter, reads one block of three counters from pinned memory, and decides
-// whether the level runs again behind a grown emission buffer.
+// loop nemo_lineage_cuts' (lin_host.h, k_lineage.hip, lin_api.h's lin_levels).  The host drives the levels: per level it
+// queues the evaluation on either tier, the cross-run count and the filter, reads one block of three counters from
+// pinned memory, and decides whether the level runs again behind a grown emission buffer.
 #include "gcut_host.h"
 #include "knock_api.h"
+#include "lin_api.h"
 
 // What a workgroup of k_lgc_lds takes of a CU's LDS beside its dynamic part: the kernel's static LDS (the chunk's keys,
 // a scan of 64 lengths and offsets, four words), rounded up generously as k_lin_lds's.  A value too small cannot cost a
@@ -135,7 +136,7 @@ int nemo_lineage_group_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int co
   {
     const uint64_t need[7] = {K + 1, std::max<uint64_t>(T, 1), slots + 1, slots, 2 * (uint64_t)n, 4,
                               std::max<uint64_t>(1, std::max<uint64_t>(tr.n_lds ? r_lds * rw_lds : 0ull, tr.n_glob ? r_glob * rw_glob : 0ull))};
-    if ((rc = grow_group(c, need, cs.d_lgoff, cs.d_lggrow, cs.d_lgkey, cs.d_lgval, cs.d_lgdesc, cs.d_lgctr, cs.d_lgreg))) return rc;
+    if ((rc = grow_group(c, need, cs.d_lgoff, cs.d_lggrow, cs.d_lgkey, cs.d_lgval, cs.d_lgdesc, cs.d_lg.ctr, cs.d_lgreg))) return rc;
   }
   cs.lg_off = gcuts::offsets32(group_off, n_groups);
   // (the call ends behind a wait for the stream: the caller's array outlives the copy)
@@ -153,25 +154,9 @@ int nemo_lineage_group_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int co
     if ((rc = timed(c, "k_gc_rows", b, 0, [&] { nemo::launch_gc_rows(ga, s); }))) return rc;
     bytes += 2.0 * b + 4.0 * (double)slots;
   }
-  // the emission buffer (it starts small), the frontier and the children's table; the cuts' list, counts and table
-  uint64_t kids_cap = std::max<uint64_t>(cs.d_lgkids.cap / 2, LIN_EMIT_START);
-  if ((rc = grow_drop(c, cs.d_lgkids, 2 * kids_cap)) || (rc = grow_drop(c, cs.d_lgktab, lin::table_slots(kids_cap))) ||
-      (rc = grow_drop(c, cs.d_lgfront, 2 * kids_cap)))
-    return rc;
-  uint64_t cuts_cap = std::max<uint64_t>(std::min(cs.d_lgcuts.cap / 2, cs.d_lgnl.cap), LIN_MIN_TABLE);
-  if ((rc = grow_drop(c, cs.d_lgcuts, 2 * cuts_cap)) || (rc = grow_drop(c, cs.d_lgnl, cuts_cap)) ||
-      (rc = grow_drop(c, cs.d_lgctab, lin::table_slots(cuts_cap))))
-    return rc;
-  uint64_t cslots = lin::table_slots(cuts_cap);
-  nemo::launch_zero(cs.d_lgctab.p, 4 * cslots, s);
-  nemo::launch_zero(cs.d_lgctr.p, 32, s);
-  {  // level 0's frontier: the empty set, every field LIN_PAD
-    static const uint64_t empty[2] = {~0ull, ~0ull};
-    HIPCHK(c, hipMemcpyAsync(cs.d_lgfront.p, empty, 16, hipMemcpyHostToDevice, s));
-  }
   nemo::LgcArgs a{};
   nemo::LinArgs &l = a.l;
-  l.K = (uint32_t)K, l.ctr = cs.d_lgctr.p, l.region = cs.d_lgreg.p;
+  l.region = cs.d_lgreg.p;
   a.goff = cs.d_lgoff.p, a.grow = cs.d_lggrow.p, a.n_dist = (uint32_t)D;
   a.key = cs.d_lgkey.p, a.val = cs.d_lgval.p, a.slots = slots;
   a.graph = cs.d_lgdesc.p, a.sinks = (flags & NEMO_KL_SINKS) ? 1u : 0u, a.n = (uint32_t)n, a.q = q;
@@ -180,119 +165,61 @@ int nemo_lineage_group_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int co
   // global tier adds 32 V per chunk for its two word arrays; the children are not known at the launch and are left
   // out; ops = 2 E child words per chunk, one sweep up and one pass down
   const double per_group = 8.0 + 4.0 * (double)T / (double)K;
-  uint64_t n_front = 1, n_cuts = 0;
-  uint32_t cut_sizes = 0;
-  volatile const uint64_t *hctr = c->h_lgc.p;
-  for (uint32_t d = 0; d <= max_size; d++) {
-    if ((rc = level_limit(n_front, d))) return rc;
-    cs.lg_stats[2 * d] = n_front;
-    const uint64_t grown = lin::cuts_grown(cuts_cap, n_cuts, n_front);
-    if (grown != cuts_cap) {  // every set of the level may be a cut: the list and the counts with their contents, the table anew
-      if ((rc = grow_keep(c, cs.d_lgcuts, 2 * grown, 2 * n_cuts)) || (rc = grow_keep(c, cs.d_lgnl, grown, n_cuts)) ||
-          (rc = grow_drop(c, cs.d_lgctab, lin::table_slots(grown))))
-        return rc;
-      cuts_cap = grown, cslots = lin::table_slots(grown);
-      nemo::launch_zero(cs.d_lgctab.p, 4 * cslots, s);
-      l.cuts = cs.d_lgcuts.p, l.ctab = cs.d_lgctab.p, l.cslots = cslots;
-      if ((rc = timed(c, "k_lin_rehash", 20.0 * (double)n_cuts, 0, [&] { nemo::launch_lin_rehash(l, n_cuts, s); }))) return rc;
+  auto prepare = [&](uint32_t, uint64_t, uint64_t ck) -> int {
+    if (int e = grow_drop(c, cs.d_lglost, (uint64_t)n * ck)) return e;
+    a.lost = cs.d_lglost.p, a.n_lost = cs.d_lgnl.p;
+    return NEMO_OK;
+  };
+  auto evaluate = [&](int pass, double *by, double *op) -> int {
+    const uint64_t n_front = l.n_front, ck = l.n_chunks;
+    const uint32_t d = l.size;
+    for (int tier = 0; tier < 2; tier++) {
+      const uint32_t nt = tier ? tr.n_glob : tr.n_lds;
+      if (!nt) continue;
+      const uint64_t res = tier ? r_glob : r_lds;
+      const klabel::Split sp = klabel::split(nt, ck, res);
+      const uint32_t grid = klabel::grid(sp.items, res, cap);
+      double b = 0, o = 0;
+      for (uint32_t k = 0; k < nt; k++) {
+        const uint32_t g = desc[desc[n + (tier ? tr.n_lds : 0) + k]];
+        const double V = (double)cs.nv(g), E = (double)cs.ne(g), L = (double)cs.kl_nlev[g];
+        b += sp.parts * (wit::image_bytes(V, E, L) + 8.0 * V) + 16.0 * (double)n_front + 64.0 * d * per_group * (double)ck +
+             (double)ck * (8.0 + (tier ? 32.0 * V : 0.0));
+        o += (double)ck * 2.0 * E;
+      }
+      a.pos = cs.d_lgdesc.p + n + (tier ? tr.n_lds : 0);
+      a.n_tier = nt, a.parts = sp.parts;
+      l.lds_total = tier ? 0u : lds_total;
+      l.region_words = tier ? rw_glob : rw_lds;
+      a.glob_words = tier ? glob_words : 0;
+      int e;
+      if (tier) e = timed(c, "k_lgc_glob", b, o, [&] { nemo::launch_lgc_glob(cs.dc, a, grid, s); });
+      else e = timed(c, "k_lgc_lds", b, o, [&] { nemo::launch_lgc_lds(cs.dc, a, grid, s); });
+      if (e) return e;
+      *by += b, *op += o;
     }
-    const bool emit = d < max_size;
-    const uint64_t ck = lin::chunks(n_front);
-    if ((rc = grow_drop(c, cs.d_lglost, (uint64_t)n * ck))) return rc;
-    uint64_t counted = 0;
-    for (int pass = 0;; pass++) {
-      nemo::launch_zero(cs.d_lgctr.p + 1, 16, s);
-      l.front = cs.d_lgfront.p, l.n_front = (uint32_t)n_front, l.n_chunks = (uint32_t)ck;
-      l.emit = emit ? 1u : 0u, l.redo = pass ? 1u : 0u;
-      l.kids = cs.d_lgkids.p, l.kids_cap = kids_cap;
-      l.cuts = cs.d_lgcuts.p, l.ctab = cs.d_lgctab.p, l.cslots = cslots;
-      l.next = cs.d_lgfront.p, l.cut_sizes = cut_sizes, l.size = d, l.cuts_before = n_cuts;
-      a.lost = cs.d_lglost.p, a.n_lost = cs.d_lgnl.p;
-      for (int tier = 0; tier < 2; tier++) {
-        const uint32_t nt = tier ? tr.n_glob : tr.n_lds;
-        if (!nt) continue;
-        const uint64_t res = tier ? r_glob : r_lds;
-        const klabel::Split sp = klabel::split(nt, ck, res);
-        const uint32_t grid = klabel::grid(sp.items, res, cap);
-        double b = 0, o = 0;
-        for (uint32_t k = 0; k < nt; k++) {
-          const uint32_t g = desc[desc[n + (tier ? tr.n_lds : 0) + k]];
-          const double V = (double)cs.nv(g), E = (double)cs.ne(g), L = (double)cs.kl_nlev[g];
-          b += sp.parts * (wit::image_bytes(V, E, L) + 8.0 * V) + 16.0 * (double)n_front + 64.0 * d * per_group * (double)ck +
-               (double)ck * (8.0 + (tier ? 32.0 * V : 0.0));
-          o += (double)ck * 2.0 * E;
-        }
-        a.pos = cs.d_lgdesc.p + n + (tier ? tr.n_lds : 0);
-        a.n_tier = nt, a.parts = sp.parts;
-        l.lds_total = tier ? 0u : lds_total;
-        l.region_words = tier ? rw_glob : rw_lds;
-        a.glob_words = tier ? glob_words : 0;
-        if (tier) rc = timed(c, "k_lgc_glob", b, o, [&] { nemo::launch_lgc_glob(cs.dc, a, grid, s); });
-        else rc = timed(c, "k_lgc_lds", b, o, [&] { nemo::launch_lgc_lds(cs.dc, a, grid, s); });
-        if (rc) return rc;
-        bytes += b, ops += o;
-      }
-      if (!pass) {  // the cuts of the level; a second pass finds them in place
-        const double bc = 8.0 * (double)n * (double)ck + 16.0 * (double)n_front;
-        if ((rc = timed(c, "k_lgc_cuts", bc, 0, [&] { nemo::launch_lgc_cuts(a, s); }))) return rc;
-        bytes += bc;
-      }
-      if (emit) {
-        const uint64_t most = std::min(kids_cap, lgc::emit_bound(n, n_front, K, d));
-        l.ktab = cs.d_lgktab.p, l.kslots = lin::table_slots(most);
-        nemo::launch_zero(cs.d_lgktab.p, 4 * l.kslots, s);
-        const double bf = 4.0 * (double)l.kslots;
-        if ((rc = timed(c, "k_lin_filter", bf, 0, [&] { nemo::launch_lin_filter(l, lin::filter_grid(most, LIN_BLOCK, 8ull * cs.dc.n_cu), s); })))
-          return rc;
-        bytes += bf;
-      }
-      nemo::launch_to_host(c->h_lgc.p, cs.d_lgctr.p, 32, s);
-      if ((rc = wait_copied(c, c->ev_lgc))) return rc;
-      counted = hctr[1];
-      const lgc::LevelEnd end = emit ? lgc::level_end(counted, kids_cap, c->opt.lin_children_max, pass) : lgc::LEVEL_DONE;
-      if (end == lgc::LEVEL_DONE) break;
-      if (end == lgc::LEVEL_LIMIT)
-        return fail(c, NEMO_ERR_LIMIT,
-                    "nemo_lineage_group_cuts: level %u emits %llu children, more than the option \"lineage_children_max\" allows (%llu): raise it, or shorten the group list or the run list",
-                    d, (unsigned long long)counted, (unsigned long long)c->opt.lin_children_max);
-      if (end == lgc::LEVEL_BROKEN)
-        return fail(c, NEMO_ERR_HIP, "nemo_lineage_group_cuts: level %u counted %llu children behind a buffer grown to its first count", d,
-                    (unsigned long long)counted);
-      // the level overflowed: the buffer to the counted size, the frontier kept, and the level once more
-      kids_cap = lin::emit_grown(kids_cap, counted);
-      if ((rc = grow_drop(c, cs.d_lgkids, 2 * kids_cap)) || (rc = grow_drop(c, cs.d_lgktab, lin::table_slots(kids_cap))) ||
-          (rc = grow_keep(c, cs.d_lgfront, 2 * kids_cap, 2 * n_front)))
-        return rc;
-    }
-    const uint64_t cuts_now = hctr[0];
-    cs.lg_stats[2 * d + 1] = cuts_now - n_cuts;
-    if (cuts_now > n_cuts) cut_sizes |= 1u << d;
-    n_cuts = cuts_now;
-    if (!emit) break;
-    n_front = hctr[2];
-    if (!n_front) break;
-  }
+    if (pass) return NEMO_OK;  // the cuts of the level; a second pass finds them in place
+    const double bc = 8.0 * (double)n * (double)ck + 16.0 * (double)n_front;
+    *by += bc;
+    return timed(c, "k_lgc_cuts", bc, 0, [&] { nemo::launch_lgc_cuts(a, s); });
+  };
+  auto emit_bound = [&](uint64_t n_front, uint32_t d) { return lgc::emit_bound(n, n_front, K, d); };
+  uint64_t n_cuts = 0;
+  if ((rc = lin_levels(c, who, "group list or the run list", cs.d_lg, c->h_lgc, c->ev_lgc, l, K, max_size, cs.lg_stats, &cs.d_lgnl, level_limit,
+                       prepare, evaluate, emit_bound, &bytes, &ops, &n_cuts)))
+    return rc;
   timer.done(bytes, ops);
-  // the cuts' keys and counts to the host; the rows sorted by (size, colex)
-  std::vector<lin::Key> keys(n_cuts);
-  std::vector<uint32_t> order(n_cuts), nl(n_cuts);
-  if (n_cuts) {
-    if ((rc = c->h_lgc.grow(c, 2 * n_cuts + n_cuts / 2 + 1))) return rc;
-    nemo::launch_to_host(c->h_lgc.p, cs.d_lgcuts.p, 16 * n_cuts, s);
-    nemo::launch_to_host(c->h_lgc.p + 2 * n_cuts, cs.d_lgnl.p, 4 * n_cuts, s);
-    if ((rc = wait_copied(c, c->ev_lgc))) return rc;
-    const uint32_t *hn = reinterpret_cast<const uint32_t *>(c->h_lgc.p + 2 * n_cuts);
-    for (uint64_t i = 0; i < n_cuts; i++) keys[i] = lin::Key{c->h_lgc.p[2 * i], c->h_lgc.p[2 * i + 1]}, nl[i] = hn[i], order[i] = (uint32_t)i;
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return lin::row_less(keys[x], keys[y]); });
-  }
+  // the rows, sorted by (size, colex), and their counts
+  LinCuts cuts;
+  if ((rc = lin_sorted_keys(c, cs.d_lg, &cs.d_lgnl, c->h_lgc, c->ev_lgc, n_cuts, &cuts))) return rc;
   cs.lg_rows.resize(n_cuts);
   cs.lg_nlost.resize(n_cuts);
   for (uint64_t i = 0; i < n_cuts; i++) {
     nemo_lineage_group_cut &row = cs.lg_rows[i];
     uint32_t pos[LIN_MAX_SIZE];
-    row.size = lin::key_unpack(keys[order[i]], pos);
+    row.size = lin::key_unpack(cuts.keys[cuts.order[i]], pos);
     for (uint32_t j = 0; j < LIN_MAX_SIZE; j++) row.group[j] = j < row.size ? pos[j] : 0xFFFFFFFFu;
-    cs.lg_nlost[i] = nl[order[i]];
+    cs.lg_nlost[i] = cuts.col[cuts.order[i]];
   }
   cs.lg_done = true;
   return NEMO_OK;

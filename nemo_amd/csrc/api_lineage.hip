@@ -1,9 +1,11 @@
 // api_lineage.hip — nemo_lineage_cuts and its fetches (k_lineage.hip, lin_host.h; DESIGN.md §Lineage-driven cut
 // search).  The level counts, the tier rule and image (wit_host.h: the witness calls'), the launch's dynamic LDS, the
 // wait for the copies, the buffer group and the timing group are knock_api.h's and ctx.h's, shared with the knock-out
-// family.  The host drives the levels: per level it queues the evaluation and the filter, reads one block of three
-// counters from pinned memory, and decides whether the level runs again behind a grown emission buffer.
+// family.  The host drives the levels (lin_api.h's lin_levels, shared with nemo_lineage_group_cuts): per level it
+// queues the evaluation and the filter, reads one block of three counters from pinned memory, and decides whether the
+// level runs again behind a grown emission buffer.
 #include "knock_api.h"
+#include "lin_api.h"
 
 namespace {
 
@@ -94,7 +96,7 @@ int nemo_lineage_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t 
   const uint64_t resident = lds ? res_lds : klabel::region_grid(2ull * cs.dc.n_cu, rw);
   {
     const uint64_t need[3] = {std::max<uint64_t>(K, 1), 4, std::max<uint64_t>(1, rw * lin::grid(~0ull, resident, cap))};
-    if ((rc = grow_group(c, need, cs.d_lncand, cs.d_lnctr, cs.d_lnreg))) return rc;
+    if ((rc = grow_group(c, need, cs.d_lncand, cs.d_ln.ctr, cs.d_lnreg))) return rc;
   }
   if (cand) {
     cs.lin_cand.assign(cand, cand + K);
@@ -114,107 +116,41 @@ int nemo_lineage_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t 
   } else {
     cs.lin_cand.clear();
   }
-  // the emission buffer (it starts small), the frontier and the children's table; the cuts' list and table
-  uint64_t kids_cap = std::max<uint64_t>(cs.d_lnkids.cap / 2, LIN_EMIT_START);
-  if ((rc = grow_drop(c, cs.d_lnkids, 2 * kids_cap)) || (rc = grow_drop(c, cs.d_lnktab, lin::table_slots(kids_cap))) ||
-      (rc = grow_drop(c, cs.d_lnfront, 2 * kids_cap)))
-    return rc;
-  uint64_t cuts_cap = std::max<uint64_t>(cs.d_lncuts.cap / 2, LIN_MIN_TABLE);
-  if ((rc = grow_drop(c, cs.d_lncuts, 2 * cuts_cap)) || (rc = grow_drop(c, cs.d_lnctab, lin::table_slots(cuts_cap)))) return rc;
-  uint64_t cslots = lin::table_slots(cuts_cap);
-  nemo::launch_zero(cs.d_lnctab.p, 4 * cslots, s);
-  nemo::launch_zero(cs.d_lnctr.p, 32, s);
-  {  // level 0's frontier: the empty set, every field LIN_PAD
-    static const uint64_t empty[2] = {~0ull, ~0ull};
-    HIPCHK(c, hipMemcpyAsync(cs.d_lnfront.p, empty, 16, hipMemcpyHostToDevice, s));
-  }
   nemo::LinArgs a{};
-  a.graph = g, a.cand = cs.d_lncand.p, a.K = (uint32_t)K, a.ctr = cs.d_lnctr.p;
+  a.graph = g, a.cand = cs.d_lncand.p;
   a.lds_total = lds_total, a.region = cs.d_lnreg.p, a.region_words = rw;
   const double img = wit::image_bytes((double)V, (double)E, (double)L);
-  uint64_t n_front = 1, n_cuts = 0;
-  uint32_t cut_sizes = 0;
-  volatile const uint64_t *hctr = c->h_lin.p;
-  for (uint32_t d = 0; d <= max_size; d++) {
-    if (!lin::front_fits(n_front))
-      return fail(c, NEMO_ERR_LIMIT, "nemo_lineage_cuts: a frontier of %llu sets of size %u exceeds 2^32 - 2: shorten the candidate list",
-                  (unsigned long long)n_front, d);
-    cs.lin_stats[2 * d] = n_front;
-    const uint64_t grown = lin::cuts_grown(cuts_cap, n_cuts, n_front);
-    if (grown != cuts_cap) {  // every set of the level may be a cut: the list with its contents, the table anew
-      if ((rc = grow_keep(c, cs.d_lncuts, 2 * grown, 2 * n_cuts)) || (rc = grow_drop(c, cs.d_lnctab, lin::table_slots(grown)))) return rc;
-      cuts_cap = grown, cslots = lin::table_slots(grown);
-      nemo::launch_zero(cs.d_lnctab.p, 4 * cslots, s);
-      a.cuts = cs.d_lncuts.p, a.ctab = cs.d_lnctab.p, a.cslots = cslots;
-      if ((rc = timed(c, "k_lin_rehash", 20.0 * (double)n_cuts, 0, [&] { nemo::launch_lin_rehash(a, n_cuts, s); }))) return rc;
-    }
-    const bool emit = d < max_size;
-    const uint64_t ck = lin::chunks(n_front);
+  auto level_limit = [&](uint64_t n_front, uint32_t d) -> int {
+    if (lin::front_fits(n_front)) return NEMO_OK;
+    return fail(c, NEMO_ERR_LIMIT, "nemo_lineage_cuts: a frontier of %llu sets of size %u exceeds 2^32 - 2: shorten the candidate list",
+                (unsigned long long)n_front, d);
+  };
+  auto prepare = [](uint32_t, uint64_t, uint64_t) { return NEMO_OK; };  // nothing is sized by the level
+  auto evaluate = [&](int, double *by, double *op) -> int {
+    const uint64_t ck = a.n_chunks;
     const uint32_t grid = lin::grid(ck, resident, cap);
-    uint64_t counted = 0;
-    for (int attempt = 0;; attempt++) {
-      nemo::launch_zero(cs.d_lnctr.p + 1, 16, s);
-      a.front = cs.d_lnfront.p, a.n_front = (uint32_t)n_front, a.n_chunks = (uint32_t)ck;
-      a.emit = emit ? 1u : 0u, a.redo = attempt ? 1u : 0u;
-      a.kids = cs.d_lnkids.p, a.kids_cap = kids_cap;
-      a.cuts = cs.d_lncuts.p, a.ctab = cs.d_lnctab.p, a.cslots = cslots;
-      a.next = cs.d_lnfront.p, a.cut_sizes = cut_sizes, a.size = d, a.cuts_before = n_cuts;
-      // the byte model: a workgroup reads the image once (wit_host.h); a set is 16 bytes read; the global tier adds
-      // 32 V per chunk for its two word arrays; the children are not known at the launch and are left out; ops = 2 E
-      // child words per chunk, one sweep up and one pass down
-      const double b = grid * img + 16.0 * (double)n_front + (lds ? 0.0 : (double)ck * 32.0 * (double)V), o = (double)ck * 2.0 * (double)E;
-      if (lds) rc = timed(c, "k_lin_lds", b, o, [&] { nemo::launch_lin_lds(cs.dc, a, grid, s); });
-      else rc = timed(c, "k_lin_glob", b, o, [&] { nemo::launch_lin_glob(cs.dc, a, grid, s); });
-      if (rc) return rc;
-      bytes += b, ops += o;
-      if (emit) {
-        const uint64_t most = std::min(kids_cap, lin::emit_bound(n_front, K, d));
-        a.ktab = cs.d_lnktab.p, a.kslots = lin::table_slots(most);
-        nemo::launch_zero(cs.d_lnktab.p, 4 * a.kslots, s);
-        const double bf = 4.0 * (double)a.kslots;
-        if ((rc = timed(c, "k_lin_filter", bf, 0, [&] { nemo::launch_lin_filter(a, lin::filter_grid(most, LIN_BLOCK, 8ull * cs.dc.n_cu), s); })))
-          return rc;
-        bytes += bf;
-      }
-      nemo::launch_to_host(c->h_lin.p, cs.d_lnctr.p, 32, s);
-      if ((rc = wait_copied(c, c->ev_lin))) return rc;
-      counted = hctr[1];
-      if (!emit || counted <= kids_cap) break;
-      if (counted > c->opt.lin_children_max) break;  // reported below
-      if (attempt) return fail(c, NEMO_ERR_HIP, "nemo_lineage_cuts: level %u counted %llu children behind a buffer grown to its first count", d, (unsigned long long)counted);
-      // the level overflowed: the buffer to the counted size, the frontier kept, and the level once more
-      kids_cap = lin::emit_grown(kids_cap, counted);
-      if ((rc = grow_drop(c, cs.d_lnkids, 2 * kids_cap)) || (rc = grow_drop(c, cs.d_lnktab, lin::table_slots(kids_cap))) ||
-          (rc = grow_keep(c, cs.d_lnfront, 2 * kids_cap, 2 * n_front)))
-        return rc;
-    }
-    if (emit && counted > c->opt.lin_children_max)
-      return fail(c, NEMO_ERR_LIMIT,
-                  "nemo_lineage_cuts: level %u emits %llu children, more than the option \"lineage_children_max\" allows (%llu): raise it, or shorten the candidate list",
-                  d, (unsigned long long)counted, (unsigned long long)c->opt.lin_children_max);
-    const uint64_t cuts_now = hctr[0];
-    cs.lin_stats[2 * d + 1] = cuts_now - n_cuts;
-    if (cuts_now > n_cuts) cut_sizes |= 1u << d;
-    n_cuts = cuts_now;
-    if (!emit) break;
-    n_front = hctr[2];
-    if (!n_front) break;
-  }
+    // the byte model: a workgroup reads the image once (wit_host.h); a set is 16 bytes read; the global tier adds
+    // 32 V per chunk for its two word arrays; the children are not known at the launch and are left out; ops = 2 E
+    // child words per chunk, one sweep up and one pass down
+    const double b = grid * img + 16.0 * (double)a.n_front + (lds ? 0.0 : (double)ck * 32.0 * (double)V), o = (double)ck * 2.0 * (double)E;
+    *by += b, *op += o;
+    if (lds) return timed(c, "k_lin_lds", b, o, [&] { nemo::launch_lin_lds(cs.dc, a, grid, s); });
+    return timed(c, "k_lin_glob", b, o, [&] { nemo::launch_lin_glob(cs.dc, a, grid, s); });
+  };
+  auto emit_bound = [&](uint64_t n_front, uint32_t d) { return lin::emit_bound(n_front, K, d); };
+  uint64_t n_cuts = 0;
+  if ((rc = lin_levels(c, who, "candidate list", cs.d_ln, c->h_lin, c->ev_lin, a, K, max_size, cs.lin_stats, nullptr, level_limit, prepare, evaluate,
+                       emit_bound, &bytes, &ops, &n_cuts)))
+    return rc;
   timer.done(bytes, ops);
-  // the cuts' keys to the host; the rows sorted by (size, colex)
-  std::vector<lin::Key> keys(n_cuts);
-  if (n_cuts) {
-    if ((rc = c->h_lin.grow(c, 2 * n_cuts))) return rc;
-    nemo::launch_to_host(c->h_lin.p, cs.d_lncuts.p, 16 * n_cuts, s);
-    if ((rc = wait_copied(c, c->ev_lin))) return rc;
-    for (uint64_t i = 0; i < n_cuts; i++) keys[i] = lin::Key{c->h_lin.p[2 * i], c->h_lin.p[2 * i + 1]};
-    std::sort(keys.begin(), keys.end(), lin::row_less);
-  }
+  // the rows, sorted by (size, colex)
+  LinCuts cuts;
+  if ((rc = lin_sorted_keys(c, cs.d_ln, nullptr, c->h_lin, c->ev_lin, n_cuts, &cuts))) return rc;
   cs.lin_rows.resize(n_cuts);
   for (uint64_t i = 0; i < n_cuts; i++) {
     nemo_lineage_cut &row = cs.lin_rows[i];
     uint32_t pos[LIN_MAX_SIZE];
-    row.size = lin::key_unpack(keys[i], pos);
+    row.size = lin::key_unpack(cuts.keys[cuts.order[i]], pos);
     for (uint32_t j = 0; j < LIN_MAX_SIZE; j++) row.node[j] = j < row.size ? cs.lin_cand[pos[j]] : 0xFFFFFFFFu;
   }
   cs.lin_done = true;

@@ -111,6 +111,20 @@ struct DevBuf {
   }
 };
 
+// The buffers of a lineage search's level loop (lin_api.h's lin_levels): nemo_lineage_cuts and nemo_lineage_group_cuts
+// keep one group each.  Each grows alone inside its call, to the largest request so far, behind a wait for the
+// stream: kids and ktab, their contents dropped, and front, its sets kept, when a level counted more children than
+// the emission buffer holds; cuts, its keys kept, and ctab, filled again from them, before a level that could overfill
+// them.  ctr grows with the call's first group.
+struct LinBufs {
+  DevBuf<unsigned long long> ctr;  // [4] cuts so far | children counted | the next frontier's sets | unused
+  DevBuf<uint64_t> kids;           // [cap][2] the children a level emits
+  DevBuf<uint64_t> front;          // [cap][2] the frontier
+  DevBuf<uint32_t> ktab;           // the children's table: lin::table_slots(cap)
+  DevBuf<uint64_t> cuts;           // [cap][2] the cuts found so far
+  DevBuf<uint32_t> ctab;           // the cuts' table: lin::table_slots(cap)
+};
+
 // Graph g = nodes [node_off[g], node_off[g + 1]), edges likewise; run r's graphs are 2r (pre) and 2r + 1 (post).
 struct GraphSizes {
   std::vector<uint64_t> node_off, edge_off;
@@ -439,10 +453,8 @@ struct CorpusState : GraphSizes {
   // lineage-driven cut search (k_lineage.hip): the call's own state, void after the next nemo_lineage_cuts or load;
   // independent of every other call's state (kl_nlev above is the load's, not a result).  One group d_ln*, which grows
   // only inside nemo_lineage_cuts, each buffer to the largest request so far, behind a wait for the stream: d_lndesc
-  // alone, before anything is counted; d_lncand, d_lnctr and d_lnreg together once the candidates are known, in this
-  // order; d_lnkids and d_lnktab, their contents dropped, and d_lnfront, its sets kept, when a level counted more
-  // children than the emission buffer holds; d_lncuts, its keys kept, and d_lnctab, filled again from them, before a
-  // level that could overfill them
+  // alone, before anything is counted; d_lncand, d_ln.ctr and d_lnreg together once the candidates are known, in this
+  // order; the rest of d_ln as LinBufs states
   bool lin_done = false;
   uint64_t lin_stats[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size 0..8: sets evaluated, minimal cuts
   std::vector<nemo_lineage_cut> lin_rows;  // the last call's rows, sorted
@@ -450,21 +462,15 @@ struct CorpusState : GraphSizes {
   uint32_t lin_up[4] = {0, 0, 0, 0};  // the last call's uploads to d_lndesc
   DevBuf<uint32_t> d_lndesc;         // [8] k_ko_leaves' list, offsets and counts for the one graph (cand == NULL)
   DevBuf<uint32_t> d_lncand;         // [K] candidate position -> node
-  DevBuf<unsigned long long> d_lnctr;  // [4] cuts so far | children counted | the next frontier's sets | unused
   DevBuf<uint64_t> d_lnreg;          // k_lin_glob: dead and need words of every workgroup of the launch
-  DevBuf<uint64_t> d_lnkids;         // [cap][2] the children a level emits
-  DevBuf<uint64_t> d_lnfront;        // [cap][2] the frontier
-  DevBuf<uint32_t> d_lnktab;         // the children's table: lin::table_slots(cap)
-  DevBuf<uint64_t> d_lncuts;         // [cap][2] the cuts found so far
-  DevBuf<uint32_t> d_lnctab;         // the cuts' table: lin::table_slots(cap)
+  LinBufs d_ln;                      // the level loop's
 
   // lineage cut search over fault events (k_lgcuts.hip): the call's own state, void after the next
   // nemo_lineage_group_cuts or load; independent of every other call's state (kl_nlev above is the load's, not a
   // result).  One group d_lg*, which grows only inside nemo_lineage_group_cuts, each buffer to the largest request so
-  // far, behind a wait for the stream: the first seven together once the call is checked, in this order; d_lglost
-  // alone before a level of more chunks; d_lgkids and d_lgktab, their contents dropped, and d_lgfront, its sets kept,
-  // when a level counted more children than the emission buffer holds; d_lgcuts and d_lgnl, their contents kept, and
-  // d_lgctab, filled again from the keys, before a level that could overfill them
+  // far, behind a wait for the stream: the first five, d_lg.ctr and d_lgreg together once the call is checked, in this
+  // order; d_lglost alone before a level of more chunks; the rest of d_lg as LinBufs states, d_lgnl, its counts kept,
+  // alongside d_lg.cuts
   bool lg_done = false;
   uint64_t lg_stats[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size 0..8: sets evaluated, minimal cuts
   std::vector<nemo_lineage_group_cut> lg_rows;  // the last call's rows, sorted,
@@ -476,15 +482,10 @@ struct CorpusState : GraphSizes {
   DevBuf<uint32_t> d_lgkey;          // the table's keys; then the rows handed out (one word)
   DevBuf<uint32_t> d_lgval;          // ... and rows
   DevBuf<uint32_t> d_lgdesc;         // [2 n]
-  DevBuf<unsigned long long> d_lgctr;  // [4] cuts so far | children counted | the next frontier's sets | unused
   DevBuf<uint64_t> d_lgreg;          // the workgroups' regions: k_lgc_glob's dead and need words, the rows' need words, the hit list's rest
   DevBuf<uint64_t> d_lglost;         // [n][chunks] a level's lost words
-  DevBuf<uint64_t> d_lgkids;         // [cap][2] the children a level emits
-  DevBuf<uint64_t> d_lgfront;        // [cap][2] the frontier
-  DevBuf<uint32_t> d_lgktab;         // the children's table: lin::table_slots(cap)
-  DevBuf<uint64_t> d_lgcuts;         // [cap][2] the cuts found so far
-  DevBuf<uint32_t> d_lgnl;           // [cap] their lost counts
-  DevBuf<uint32_t> d_lgctab;         // the cuts' table: lin::table_slots(cap)
+  LinBufs d_lg;                      // the level loop's
+  DevBuf<uint32_t> d_lgnl;           // [cap] the cuts' lost counts
 
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them

@@ -46,6 +46,25 @@ __device__ __forceinline__ uint64_t lgc_wave_or(uint64_t w) {
   return w;
 }
 
+// This lane's OR of fetch(e) over e in [lo, hi).  A whole wave calls it, a lane per range: a short range is walked by
+// its own lane, a long one (is_long) by the whole wave, one long range at a time.
+template <class F>
+__device__ __forceinline__ uint64_t lgc_range_or(uint32_t lo, uint32_t hi, bool is_long, F &&fetch) {
+  const uint32_t lane = lane_id();
+  uint64_t w = 0ull;
+  if (!is_long)
+    for (uint32_t e = lo; e < hi; e++) w |= fetch(e);
+  for (uint64_t hm = __ballot(is_long); hm; hm &= hm - 1ull) {  // wave-uniform
+    const int src = __ffsll((long long)hm) - 1;
+    const uint32_t hl = (uint32_t)__shfl((int)lo, src), hh = (uint32_t)__shfl((int)hi, src);
+    uint64_t part = 0ull;
+    for (uint32_t e = hl + lane; e < hh; e += 64u) part |= fetch(e);
+    part = lgc_wave_or(part);
+    if ((int)lane == src) w = part;
+  }
+  return w;
+}
+
 // One chunk ci of the frontier on the staged graph of list position pos.  rn: the D rows' need words.  Ends behind a
 // barrier.  All 256 threads.
 template <bool LDS>
@@ -62,10 +81,7 @@ __device__ __forceinline__ void lgc_chunk(const LgcArgs &a, const KoImg<LDS> &g,
   const uint32_t D = a.n_dist;
   unsigned long long *d64 = reinterpret_cast<unsigned long long *>(g.dead);
   ko_zero_dead<LDS>(g);  // its barrier: the staging's end, and the previous chunk's last reads of s_key
-  if (tid < n) {
-    const lin::Key k = lin_load(l.front, first + tid);
-    s_key[tid][0] = k.lo, s_key[tid][1] = k.hi;
-  }
+  lin_stage_keys(l.front, first, n, s_key);
   __syncthreads();
   // seeds: field j of the 64 sets at a time (every set of the level holds l.size positions).  Wave 0 scans the groups'
   // lengths, then all four waves walk the (set, label) pairs, 256 at a time: a pair whose row is empty on this graph
@@ -123,18 +139,7 @@ __device__ __forceinline__ void lgc_chunk(const LgcArgs &a, const KoImg<LDS> &g,
       const uint32_t r = base + tid;
       uint32_t lo = 0u, hi = 0u;
       if (r < D) lo = ls.lo(r), hi = ls.hi(r);
-      const bool hub = hi - lo > KO_HUB;
-      uint64_t w = 0ull;
-      if (!hub)
-        for (uint32_t e = lo; e < hi; e++) w |= wit_need<LDS>(&need[ls.get(D + 1u + e)]);
-      for (uint64_t hm = __ballot(hub); hm; hm &= hm - 1ull) {  // wave-uniform: one long row at a time
-        const int src = __ffsll((long long)hm) - 1;
-        const uint32_t hl = (uint32_t)__shfl((int)lo, src), hh = (uint32_t)__shfl((int)hi, src);
-        uint64_t part = 0ull;
-        for (uint32_t e = hl + lane; e < hh; e += 64u) part |= wit_need<LDS>(&need[ls.get(D + 1u + e)]);
-        part = lgc_wave_or(part);
-        if ((int)lane == src) w = part;
-      }
+      const uint64_t w = lgc_range_or(lo, hi, hi - lo > KO_HUB, [&](uint32_t e) { return wit_need<LDS>(&need[ls.get(D + 1u + e)]); });
       if (r < D) rn[r] = w;
     }
     if (!rn_lds) __threadfence_block();
@@ -145,30 +150,8 @@ __device__ __forceinline__ void lgc_chunk(const LgcArgs &a, const KoImg<LDS> &g,
       const uint32_t k = kb + lane;
       uint32_t beg = 0u, end = 0u;
       if (k < l.K) beg = a.goff[k], end = a.goff[k + 1u];
-      const bool big = end - beg > LGC_WAVE_GROUP;
-      uint64_t w = 0ull;
-      if (!big)
-        for (uint32_t e = beg; e < end; e++) w |= rn[a.grow[e]];
-      for (uint64_t hm = __ballot(big); hm; hm &= hm - 1ull) {  // wave-uniform: one long group at a time
-        const int src = __ffsll((long long)hm) - 1;
-        const uint32_t hl = (uint32_t)__shfl((int)beg, src), hh = (uint32_t)__shfl((int)end, src);
-        uint64_t part = 0ull;
-        for (uint32_t e = hl + lane; e < hh; e += 64u) part |= rn[a.grow[e]];
-        part = lgc_wave_or(part);
-        if ((int)lane == src) w = part;
-      }
-      w &= live;
-      uint32_t total;
-      const uint32_t pre = lin_wave_scan((uint32_t)__popcll(w), &total);
-      if (!total) continue;
-      unsigned long long at = 0;
-      if (lane == 0u) at = atomicAdd(l.ctr + 1, (unsigned long long)total);
-      at = (unsigned long long)__shfl((unsigned long long)at, 0) + pre;
-      for (; w; w &= w - 1ull, at++) {
-        if (at >= l.kids_cap) break;  // counted, not written
-        const int h = __ffsll((long long)w) - 1;
-        lin_store(l.kids, at, lin::key_insert(lin::Key{s_key[h][0], s_key[h][1]}, k));
-      }
+      const uint64_t w = lgc_range_or(beg, end, end - beg > LGC_WAVE_GROUP, [&](uint32_t e) { return rn[a.grow[e]]; });
+      lin_emit(l, s_key, k, w & live);
     }
   }
   __syncthreads();  // the image's, the words', the list's and s_key's last reads

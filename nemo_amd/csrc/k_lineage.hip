@@ -30,10 +30,7 @@ __device__ __forceinline__ void lin_chunk(const LinArgs &a, const KoImg<LDS> &g,
   const uint32_t first = ci * KO_CHUNK, n = min(KO_CHUNK, a.n_front - first);
   uint64_t *dead = g.dead;
   ko_zero_dead<LDS>(g);  // its barrier: the staging's end, and the previous chunk's last reads of s_key
-  if (tid < n) {
-    const lin::Key k = lin_load(a.front, first + tid);
-    s_key[tid][0] = k.lo, s_key[tid][1] = k.hi;
-  }
+  lin_stage_keys(a.front, first, n, s_key);
   // seeds: a thread per (set, field); several sets may name one candidate: atomic OR
   for (uint32_t t = tid; t < n * LIN_MAX_SIZE; t += KO_BLOCK) {
     const uint32_t s = t / LIN_MAX_SIZE, j = t % LIN_MAX_SIZE;
@@ -71,17 +68,7 @@ __device__ __forceinline__ void lin_chunk(const LinArgs &a, const KoImg<LDS> &g,
         const uint32_t v = a.cand[k];
         if (v < g.V) w = wit_need<LDS>(&need[v]) & live;
       }
-      uint32_t total;
-      const uint32_t pre = lin_wave_scan((uint32_t)__popcll(w), &total);
-      if (!total) continue;
-      unsigned long long at = 0;
-      if (lane == 0u) at = atomicAdd(a.ctr + 1, (unsigned long long)total);
-      at = (unsigned long long)__shfl((unsigned long long)at, 0) + pre;
-      for (; w; w &= w - 1ull, at++) {
-        if (at >= a.kids_cap) break;  // counted, not written
-        const int h = __ffsll((long long)w) - 1;
-        lin_store(a.kids, at, lin::key_insert(lin::Key{s_key[h][0], s_key[h][1]}, k));
-      }
+      lin_emit(a, s_key, k, w);
     }
   }
   __syncthreads();  // the image's, the words' and s_key's last reads

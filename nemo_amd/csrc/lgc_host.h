@@ -1,8 +1,8 @@
 // lgc_host.h — the arithmetic of nemo_lineage_group_cuts (k_lgcuts.hip; DESIGN.md §Lineage cut search over fault
 // events) as pure functions: the limits of the call and of a level, what a workgroup keeps behind its LDS image (the
 // rows' need words, then the head of the hit list) and in its region of device memory, the cross-run count that makes
-// a set a cut, and the rule by which a level runs again.  The keys, the tables, the rows' order and the emission
-// buffer are lin_host.h's, the groups' checks gcut_host.h's, the work items klabel_host.h's, the image wit_host.h's.
+// a set a cut, and the most children a level can count.  The keys, the tables, the rows' order, the emission buffer
+// and the rule by which a level runs again are lin_host.h's, the groups' checks gcut_host.h's, the work items klabel_host.h's, the image wit_host.h's.
 // No HIP and no context, so tools/lgc_host_check.cpp drives it under the host sanitizers.
 #pragma once
 #include <stddef.h>
@@ -70,18 +70,7 @@ KO_HD static inline uint32_t lost_count(const uint64_t *lost, uint64_t n, uint64
 }
 KO_HD static inline bool is_cut(uint32_t count, uint32_t q) { return q > 0 && count >= q; }
 
-// ---- a level's end -----------------------------------------------------------------------------------------
-// What follows a pass over a level that counted `counted` children (every list position's, before duplicates are
-// removed) behind an emission buffer of `cap`: the children are all there (LEVEL_DONE); the count passes the option
-// (LEVEL_LIMIT: NEMO_ERR_LIMIT); the level runs again behind a buffer of lin::emit_grown(cap, counted), its cuts in
-// place (LEVEL_AGAIN); or, on the second pass, the count passed the grown buffer, which cannot be (LEVEL_BROKEN).
-enum LevelEnd { LEVEL_DONE = 0, LEVEL_AGAIN = 1, LEVEL_LIMIT = 2, LEVEL_BROKEN = 3 };
-static inline LevelEnd level_end(uint64_t counted, uint64_t cap, uint64_t children_max, int pass) {
-  if (counted > children_max) return LEVEL_LIMIT;
-  if (counted <= cap) return LEVEL_DONE;
-  return pass ? LEVEL_BROKEN : LEVEL_AGAIN;
-}
-
+// ---- a level's children ------------------------------------------------------------------------------------
 // the most children a level can count: every list position emits every (set, candidate outside it) at most once
 static inline uint64_t emit_bound(uint64_t n, uint64_t n_front, uint64_t K, uint32_t d) {
   const uint64_t one = lin::emit_bound(n_front, K, d);

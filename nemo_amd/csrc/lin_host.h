@@ -158,6 +158,19 @@ static inline uint64_t cuts_grown(uint64_t cap, uint64_t n_cuts, uint64_t n_fron
   return need <= cap ? cap : std::max(need, 2 * cap);
 }
 
+// ---- a level's end -----------------------------------------------------------------------------------------
+// What follows a pass over a level that counted `counted` children (before duplicates are removed; the group search:
+// every list position's) behind an emission buffer of `cap`: the children are all there (LEVEL_DONE); the count
+// passes the option (LEVEL_LIMIT: NEMO_ERR_LIMIT); the level runs again behind a buffer of emit_grown(cap, counted),
+// its cuts in place (LEVEL_AGAIN); or, on the second pass, the count passed the grown buffer, which cannot be
+// (LEVEL_BROKEN).
+enum LevelEnd { LEVEL_DONE = 0, LEVEL_AGAIN = 1, LEVEL_LIMIT = 2, LEVEL_BROKEN = 3 };
+static inline LevelEnd level_end(uint64_t counted, uint64_t cap, uint64_t children_max, int pass) {
+  if (counted > children_max) return LEVEL_LIMIT;
+  if (counted <= cap) return LEVEL_DONE;
+  return pass ? LEVEL_BROKEN : LEVEL_AGAIN;
+}
+
 static inline uint64_t chunks(uint64_t n_front) { return cuts::chunks(n_front); }
 // workgroups of the persistent evaluation over n chunks: cut_host.h's rule under the option kl_grid
 static inline uint32_t grid(uint64_t n_chunks, uint64_t resident, uint32_t cap) { return cuts::grid(n_chunks, resident, cap); }

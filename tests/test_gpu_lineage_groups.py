@@ -353,6 +353,45 @@ def test_emission_limit_and_regrow(straddle):
         e.close()
 
 
+def test_both_searches_interleaved_on_one_engine(straddle):
+    """nemo_lineage_cuts (A) and nemo_lineage_group_cuts (B) share the level loop and keep a buffer group each.  On one
+    engine, A, B, A, B: the first call of either counts past its first 1024-child buffer (129 * 129 and 2 * 65 * 65
+    children) and runs the level again; every call's rows, lost counts and 18 stats are those of a fresh engine."""
+    (kinds, edges, _), groups = and_of_ors(M), straddle[1]
+    wide, wide_edges, sinks = and_of_ors(129)
+    corpus = relabel(build([(kinds, edges)] * 2 + [(wide, wide_edges)]),
+                     [list(range(len(kinds)))] * 2 + [list(range(2000000, 2000000 + len(wide)))])
+
+    def call_a(e):
+        rows = e.lineage_cuts(2, 1, None, 2)
+        return [(int(r["size"]),) + tuple(int(x) for x in r["node"]) for r in rows], e.lineage_cut_stats().tolist()
+
+    def call_b(e):
+        rows, n_lost = e.lineage_group_cuts([0, 1], 1, groups, 2)
+        return got_rows(rows), n_lost.tolist(), e.lineage_group_cut_stats().tolist()
+
+    def fresh(call):
+        e = E.Engine(0)
+        try:
+            e.load(corpus)
+            return call(e)
+        finally:
+            e.close()
+
+    want_a, want_b = fresh(call_a), fresh(call_b)
+    assert want_a[0] == [(2, sinks[2 * i], sinks[2 * i + 1]) + (NONE,) * 6 for i in range(129)]
+    assert want_a[1] == [[1, 0], [129, 0], [129 + 129 * 128 // 2, 129]] + [[0, 0]] * 6
+    assert want_b == (STRADDLE_ROWS, [2] * M, STRADDLE_STATS)
+    e = E.Engine(0)
+    try:
+        e.load(corpus)
+        for k in range(2):
+            assert call_a(e) == want_a, f"nemo_lineage_cuts, call {k + 1} of A, B, A, B"
+            assert call_b(e) == want_b, f"nemo_lineage_group_cuts, call {k + 1} of A, B, A, B"
+    finally:
+        e.close()
+
+
 # ---- 9. sizes ------------------------------------------------------------------------------------------------------------------
 def test_hub_label_and_long_group(eng, hand):
     """H2: 300 nodes of label 30 (a row past KO_HUB); a group of 70 labels of which three occur"""

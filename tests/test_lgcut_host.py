@@ -105,22 +105,42 @@ def test_host_header_reuses_and_kernels_share():
         assert name in hdr, name
     k = open(os.path.join(CSRC, "k_lgcuts.hip")).read()
     for name in ('#include "hit_list.h"', '#include "ko_sweep.h"', '#include "wit_down.h"', '#include "lin_dev.h"', "hit_list_build(",
-                 "ko_sweep<LDS>(g)", "wit_down<LDS>(g, need, n, false)", "lin::key_insert(", "lin_cut_insert(", "lgc::lost_count(",
-                 "void k_lgc_lds(", "void k_lgc_glob(", "void k_lgc_cuts("):
+                 "ko_sweep<LDS>(g)", "wit_down<LDS>(g, need, n, false)", "lin_stage_keys(", "lin_emit(", "lin_cut_insert(", "lgc::lost_count(",
+                 "uint64_t lgc_wave_or(", "uint64_t lgc_range_or(", "void k_lgc_lds(", "void k_lgc_glob(", "void k_lgc_cuts("):
         assert name in k, name
     assert "void wit_down(" not in k and "void ko_sweep(" not in k and "void k_lin_filter(" not in k
     lin = open(os.path.join(CSRC, "k_lineage.hip")).read()
     assert '#include "lin_dev.h"' in lin and "lin::Key lin_load(" not in lin  # moved, not copied
+    assert "lin_stage_keys(" in lin and "lin_emit(" in lin
     dev = open(os.path.join(CSRC, "lin_dev.h")).read()
-    for name in ("lin::Key lin_load(", "void lin_store(", "uint32_t lin_wave_scan(", "void lin_cut_insert("):
+    for name in ("lin::Key lin_load(", "void lin_store(", "uint32_t lin_wave_scan(", "void lin_cut_insert(", "void lin_stage_keys(",
+                 "void lin_emit(", "lin::key_insert("):
         assert name in dev, name
+    # the emission tail is lin_dev.h's alone: one scan, one claim on the children's cursor in the whole tree
+    assert "lin_wave_scan(" not in k and "lin_wave_scan(" not in lin and "lin::key_insert(" not in k and "lin::key_insert(" not in lin
+    claims = [f for f in sorted(os.listdir(CSRC)) if "ctr + 1," in open(os.path.join(CSRC, f)).read()]
+    assert claims == ["lin_dev.h"] and dev.count("atomicAdd(l.ctr + 1,") == 1
     api = open(os.path.join(CSRC, "api_lgcuts.hip")).read()
-    for name in ('GroupTimer timer(c, "k_lgcuts")', "launch_gc_table(", "launch_gc_rows(", "launch_lin_filter(", "launch_lin_rehash(",
-                 "grow_keep(", "grow_drop(", "ko_lds_total(", "wit::lds_fits(", "lgc::level_end("):
+    api_lin = open(os.path.join(CSRC, "api_lineage.hip")).read()
+    for name in ('GroupTimer timer(c, "k_lgcuts")', "launch_gc_table(", "launch_gc_rows(", "grow_drop(", "ko_lds_total(", "wit::lds_fits(",
+                 '#include "lin_api.h"', "lin_levels(", "lin_sorted_keys("):
         assert name in api, name
+    # the level loop, its buffers' growth and the overflow rule are lin_api.h's, once, for both calls
+    drv = open(os.path.join(CSRC, "lin_api.h")).read()
+    assert '#include "knock_api.h"' in drv
+    for name in ("launch_lin_filter(", "launch_lin_rehash(", "grow_keep(", "lin::cuts_grown(", "lin::emit_grown(", "lin::level_end("):
+        assert name in drv, name
+        assert name not in api and name not in api_lin, name
+    assert '#include "lin_api.h"' in api_lin and "lin_levels(" in api_lin and "lin_sorted_keys(" in api_lin
+    users = [f for f in sorted(os.listdir(CSRC)) if '#include "lin_api.h"' in open(os.path.join(CSRC, f)).read()]
+    assert users == ["api_lgcuts.hip", "api_lineage.hip"]
+    host = open(os.path.join(CSRC, "lin_host.h")).read()
+    assert "LevelEnd level_end(" in host and "level_end(" not in hdr  # moved, not copied
+    ctx = open(os.path.join(CSRC, "ctx.h")).read()
+    assert "struct LinBufs {" in ctx and "LinBufs d_ln;" in ctx and "LinBufs d_lg;" in ctx
     shared = open(os.path.join(CSRC, "knock_api.h")).read()
     assert "int grow_keep(" in shared and "int grow_drop(" in shared
-    assert "int grow_keep(" not in open(os.path.join(CSRC, "api_lineage.hip")).read()
+    assert "int grow_keep(" not in api_lin
 
 
 def test_host_check_program_passes_under_the_host_sanitizers(tmp_path):

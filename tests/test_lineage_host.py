@@ -112,6 +112,7 @@ def test_host_header_reuses_and_kernels_share_the_need_pass():
         assert f"void {name}(" in lin, name
     api = open(os.path.join(CSRC, "api_lineage.hip")).read()
     assert '#include "knock_api.h"' in api and 'GroupTimer timer(c, "k_lineage")' in api and "ensure_nlev(" in api and "ko_lds_total(" in api
+    assert '#include "lin_api.h"' in api and "lin_levels(" in api  # the level loop is the shared driver's
     assert "NEMO_WIT_MASKS" not in api and "nemo_witness_sets(" not in api  # fused: no witness call and a reader
 
 

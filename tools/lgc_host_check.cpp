@@ -1,5 +1,5 @@
 // lgc_host_check — drives the host side of nemo_lineage_group_cuts (nemo_amd/csrc/lgc_host.h): the limits, what a
-// workgroup keeps behind its image and in its region, the level's end, and a host model of the whole search in the steps
+// workgroup keeps behind its image and in its region, and a host model of the whole search in the steps
 // the kernels take (the keys, the lost words and the cross-run count under q, the children as a union over the list
 // positions on which a set is not lost, duplicate removal and the subset filter in the two tables, a level that runs
 // again behind a grown emission buffer without appending its cuts twice) against brute force over all subsets and
@@ -32,9 +32,6 @@ static void check_limits() {
   CHECK(lgc::level_check((1ull << 28) + 1, 1) == lgc::LEVEL_WORDS && lgc::level_check(1ull << 28, 65) == lgc::LEVEL_WORDS);
   CHECK(lgc::level_check(1, LIN_MAX_FRONT + 1) == lgc::LEVEL_FRONT && lgc::level_check(1, LIN_MAX_FRONT) == lgc::LEVEL_OK);
   CHECK(lgc::level_check(0, 5) == lgc::LEVEL_OK);
-  CHECK(lgc::level_end(10, 1024, 64, 0) == lgc::LEVEL_DONE && lgc::level_end(65, 1024, 64, 0) == lgc::LEVEL_LIMIT);
-  CHECK(lgc::level_end(1025, 1024, 1 << 20, 0) == lgc::LEVEL_AGAIN && lgc::level_end(1025, 1024, 1 << 20, 1) == lgc::LEVEL_BROKEN);
-  CHECK(lgc::level_end(1024, 1024, 1024, 1) == lgc::LEVEL_DONE && lgc::level_end(2000, 1024, 1500, 0) == lgc::LEVEL_LIMIT);
   CHECK(lgc::emit_bound(2, 65, 130, 1) == 2 * 65 * 129 && lgc::emit_bound(3, 1, 8, 0) == 24 && lgc::emit_bound(0, 5, 8, 0) == 0);
   CHECK(lgc::emit_bound(1ull << 40, 1ull << 30, 65535, 1) == ~0ull);
   CHECK(lgc::is_cut(2, 2) && lgc::is_cut(3, 2) && !lgc::is_cut(1, 2) && !lgc::is_cut(0, 0));
@@ -211,10 +208,10 @@ static Result search_model(const Problem &p, uint32_t max_size, uint64_t emit_st
           cuts_.push_back(front[s]), nl.push_back(cnt);
           CHECK(cuts_.size() <= cuts_cap && lin::table_insert(ctab.data(), cslots, cuts_.data(), (uint32_t)cuts_.size() - 1));
         }
-      const lgc::LevelEnd end = emit ? lgc::level_end(counted, kids_cap, LIN_CHILDREN_DEFAULT, pass) : lgc::LEVEL_DONE;
-      CHECK(end == lgc::LEVEL_DONE || end == lgc::LEVEL_AGAIN);
+      const lin::LevelEnd end = emit ? lin::level_end(counted, kids_cap, LIN_CHILDREN_DEFAULT, pass) : lin::LEVEL_DONE;
+      CHECK(end == lin::LEVEL_DONE || end == lin::LEVEL_AGAIN);
       CHECK(counted <= lgc::emit_bound(n, front.size(), p.groups.size(), d));
-      if (end == lgc::LEVEL_DONE) break;
+      if (end == lin::LEVEL_DONE) break;
       kids_cap = lin::emit_grown(kids_cap, counted);
       (*reruns)++;
     }

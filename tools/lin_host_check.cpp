@@ -1,8 +1,8 @@
 // lin_host_check — drives the host side of nemo_lineage_cuts (nemo_amd/csrc/lin_host.h): the keys (pack, unpack,
 // insert, subsets, equality) over every set of small universes and the edges of the u16 range, the rows' order against
 // cut_host.h's colex ranks for sizes 1..3 and against a plain comparison of reversed positions above, the subset
-// enumeration, the candidate checks (cut_host.h's, and the limit), the option's value, the table and buffer sizes, the
-// chunk and grid counts, and the table steps the kernels take (duplicate removal, the subset filter) in a host model
+// enumeration, the candidate checks (cut_host.h's, and the limit), the option's value, the table and buffer sizes, a
+// level's end, the chunk and grid counts, and the table steps the kernels take (duplicate removal, the subset filter) in a host model
 // of the whole level search on AND-of-ORs graphs against brute force, with the stats the definition gives.  Meant for
 // the host sanitizers; it calls nothing on a device:
 //   g++ -std=c++17 -g -Wall -fsanitize=address,undefined -static-libasan -static-libubsan
@@ -146,6 +146,9 @@ static void check_sizes() {
   CHECK(lin::emit_bound(5, 2, 3) == 0 && lin::emit_bound(~0ull / 2, 10, 1) == ~0ull);
   CHECK(lin::emit_grown(1024, 16641) == 16641 && lin::emit_grown(1024, 10) == 1024);
   CHECK(lin::cuts_grown(64, 0, 64) == 64 && lin::cuts_grown(64, 1, 64) == 128 && lin::cuts_grown(64, 10, 1000) == 1010);
+  CHECK(lin::level_end(10, 1024, 64, 0) == lin::LEVEL_DONE && lin::level_end(65, 1024, 64, 0) == lin::LEVEL_LIMIT);
+  CHECK(lin::level_end(1025, 1024, 1 << 20, 0) == lin::LEVEL_AGAIN && lin::level_end(1025, 1024, 1 << 20, 1) == lin::LEVEL_BROKEN);
+  CHECK(lin::level_end(1024, 1024, 1024, 1) == lin::LEVEL_DONE && lin::level_end(2000, 1024, 1500, 0) == lin::LEVEL_LIMIT);
   CHECK(lin::chunks(0) == 0 && lin::chunks(1) == 1 && lin::chunks(64) == 1 && lin::chunks(65) == 2 && lin::chunks(129) == 3);
   CHECK(lin::grid(0, 256, 0) == 1 && lin::grid(3, 256, 0) == 3 && lin::grid(1000, 256, 0) == 256 && lin::grid(1000, 256, 1) == 1);
   CHECK(lin::grid(~0ull, 512, 0) == 512 && lin::grid(~0ull, 512, 7) == 7);
