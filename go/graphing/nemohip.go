@@ -1252,6 +1252,78 @@ func (n *Neo4J) WitnessLabels(iters []uint, cond string, sets [][]uint32, all bo
 	return n.witnessRows(withMasks, nodes)
 }
 
+// MinRepair is one minimal repair of a failed run against a good one: a smallest
+// set of base events the good run has and the failed run lacks whose presence
+// would have been enough for the good run's outcome to be derived.
+type MinRepair struct {
+	Nodes  []uint32 // local node indices of the base run's post graph, in candidate-list order
+	IDs    []string // their node IDs
+	Labels []string // ... and labels
+}
+
+// RepairResult is what MinRepairs returns beside the repairs.
+type RepairResult struct {
+	Status     uint64    // C.NEMO_REPAIR_HOLDS, C.NEMO_REPAIR_SEARCHED or C.NEMO_REPAIR_BEYOND
+	Absent     uint64    // how many base events of the base run the other run lacks
+	Stats      [9]uint64 // per size 1..3: live candidates entering the round, hypotheses evaluated, minimal repairs found
+	Candidates []uint32  // the absent sink goals, in node-index order
+	Repairs    []*MinRepair
+}
+
+// MinRepairs returns all minimal repairs of at most maxSize (1..3) base events
+// of run base's post provenance against run other (nemo_min_repairs): the
+// absent set and the candidates are the sink goals of base's post graph whose
+// label is no goal label of other's post graph.  It is the exact answer to the
+// question the reference's missing-events heuristic approximates: which of the
+// missing events, had they happened, suffice together.  Status
+// C.NEMO_REPAIR_HOLDS means the absent events do not explain a failure, and
+// C.NEMO_REPAIR_BEYOND cannot occur here (every absent node is a candidate);
+// the repairs come sorted by size, then by the colex rank of their positions in
+// the list of candidates that are no repair alone.
+func (n *Neo4J) MinRepairs(base, other uint, maxSize uint) (*RepairResult, error) {
+	if err := n.err(C.nemo_min_repairs(n.ctx, C.uint32_t(base), C.uint32_t(other), C.uint32_t(maxSize), 0)); err != nil {
+		return nil, err
+	}
+	var stats [11]uint64
+	if err := n.err(C.nemo_fetch_min_repair_stats(n.ctx, (*C.uint64_t)(unsafe.Pointer(&stats[0])))); err != nil {
+		return nil, err
+	}
+	res := &RepairResult{Status: stats[0], Absent: stats[1]}
+	copy(res.Stats[:], stats[2:])
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_min_repair_cands(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	cands := make([]C.uint32_t, cnt+1) // never empty: &cands[0] below
+	if err := n.err(C.nemo_fetch_min_repair_cands(n.ctx, &cands[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	for _, v := range cands[:cnt] {
+		res.Candidates = append(res.Candidates, uint32(v))
+	}
+	if err := n.err(C.nemo_fetch_min_repairs(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	reps := make([]C.nemo_repair, cnt+1)
+	if err := n.err(C.nemo_fetch_min_repairs(n.ctx, &reps[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	p := n.graphs[2*n.runIdx[base]+1]
+	for _, rep := range reps[:cnt] {
+		m := &MinRepair{}
+		for j := 0; j < int(rep.size); j++ {
+			v := uint32(rep.node[j])
+			id, label := "", ""
+			if int(v) < len(p.goals) {
+				id, label = p.goals[v].ID, p.goals[v].Label
+			}
+			m.Nodes, m.IDs, m.Labels = append(m.Nodes, v), append(m.IDs, id), append(m.Labels, label)
+		}
+		res.Repairs = append(res.Repairs, m)
+	}
+	return res, nil
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

@@ -630,6 +630,75 @@ int nemo_fetch_min_cuts(nemo_ctx *ctx, nemo_cut *out, uint64_t cap, uint64_t *n_
  * hypotheses evaluated, minimal cuts found (zeros for s > max_size).           */
 int nemo_fetch_min_cut_stats(nemo_ctx *ctx, uint64_t out[9]);
 
+/* ---- minimal repair sets: the fewest missing events that restore a run's outcome ----
+ * The monotone dual of nemo_min_cuts.  The subject (a raw loaded graph
+ * g = 2r + cond), dead_F(v), the roots and "the outcome is lost under F" are the
+ * knock-out definitions above, unchanged.
+ * A is the absent set: nodes of g assumed lost.  cand is a subset of A: the nodes
+ * that may be restored.  For S within cand the outcome holds under S iff it is
+ * not lost under F = A \ S.  A repair is an S under which the outcome holds; it
+ * is minimal if no proper subset of it is a repair.  "Holds" is monotone in S, so
+ * every superset of a repair is a repair.  The call returns all minimal repairs
+ * of size <= max_size; max_size must be 1, 2 or 3 and flags 0 (NEMO_ERR_INVALID
+ * otherwise, "max_size must be 1, 2 or 3").
+ * Status: round 0 is one chunk of two hypotheses, S = {} and S = cand.
+ *   NEMO_REPAIR_HOLDS    the outcome already holds under S = {}: the absent
+ *                        events do not explain a failure.  Also a graph without
+ *                        roots, and an empty A.  Zero rows.
+ *   NEMO_REPAIR_BEYOND   the outcome is lost even under S = cand: some absent
+ *                        node outside cand is needed by every derivation.  Zero
+ *                        rows.
+ *   NEMO_REPAIR_SEARCHED otherwise: the rows are all minimal repairs of size
+ *                        <= max_size (there may be none that small).
+ * Rounds, ranks, row order and limits are nemo_min_cuts', with "cut" read as
+ * "repair": round 1 evaluates the K singletons; the candidates that are no
+ * repair alone form the live list, in candidate order, K1 entries; round 2
+ * evaluates all C(K1,2) pairs of live positions, and every holding pair is
+ * minimal; round 3 evaluates all C(K1,3) triples, and a holding triple is
+ * minimal iff none of its three pairs held.  Live positions a < b < c have the
+ * colex rank C(c,3) + C(b,2) + a; the rows are sorted by (size, rank).  A row's
+ * nodes are node indices in candidate-list order, unused entries UINT32_MAX.
+ * More than 2^32 - 2 hypotheses in one round is NEMO_ERR_LIMIT (shorten the
+ * candidate list); the call then leaves no results.  Rounds 0 and 1 run back to
+ * back, so round 1 runs whatever the status is.
+ * nemo_min_repair_sets: the caller names both lists, graph-local node indices of
+ * any kind.  cand == NULL means cand = absent, in its order.  NEMO_ERR_INVALID,
+ * checked on the host in this order before anything is uploaded, with a message
+ * that names the position in its list: an absent node >= V_g; an absent node
+ * listed twice; a candidate listed twice; a candidate that is not in absent.
+ * cond outside 0 / 1 is NEMO_ERR_INVALID.
+ * nemo_min_repairs: the pair form.  g is the base run's raw post graph, and
+ * A = cand = the sink goals of g (goals without children) whose label is no goal
+ * label of the other run's post graph, in node-index order: nemo_diffprov_pairs'
+ * label test, restricted to sinks.  Both lists are made on the device.
+ * (x, x) gives an empty A, NEMO_REPAIR_HOLDS and zero rows.  The call needs what
+ * nemo_diffprov_pairs needs (NEMO_ERR_STATE before nemo_mark_holds).
+ * nemo_fetch_min_repair_cands returns the candidate list the call used: rows
+ * name nodes, and the stats name K.
+ * An iteration that is not loaded is NEMO_ERR_NOTFOUND; a node context and a call
+ * with no corpus loaded return NEMO_ERR_STATE.  The calls block until the rows are
+ * on the host.  The results are the two calls' own state: valid until the next
+ * of them or nemo_load_corpus (the fetches return NEMO_ERR_STATE otherwise),
+ * independent of every other call's state in both directions.                    */
+#define NEMO_REPAIR_HOLDS 0
+#define NEMO_REPAIR_SEARCHED 1
+#define NEMO_REPAIR_BEYOND 2
+typedef struct nemo_repair {
+  uint32_t size;    /* 1..3                                                          */
+  uint32_t node[3]; /* nodes in candidate-list order, unused = UINT32_MAX            */
+} nemo_repair;      /* nemo_cut's layout                                             */
+int nemo_min_repair_sets(nemo_ctx *ctx, uint32_t iteration, int cond, const uint32_t *absent, size_t n_absent,
+                         const uint32_t *cand, size_t n_cand, uint32_t max_size, uint32_t flags);
+int nemo_min_repairs(nemo_ctx *ctx, uint32_t base_iter, uint32_t other_iter, uint32_t max_size, uint32_t flags);
+/* out[k] for every minimal repair k; out == NULL queries *n_out.               */
+int nemo_fetch_min_repairs(nemo_ctx *ctx, nemo_repair *out, uint64_t cap, uint64_t *n_out);
+/* out[0]: the status; out[1]: |A|; out[2 + 3 (s - 1) ..] per size s = 1..3: live
+ * candidates entering the round, hypotheses evaluated, minimal repairs found
+ * (zeros for s > max_size, and all nine zero unless NEMO_REPAIR_SEARCHED).      */
+int nemo_fetch_min_repair_stats(nemo_ctx *ctx, uint64_t out[11]);
+/* out[p] = the node of candidate position p; out == NULL queries *n_out.       */
+int nemo_fetch_min_repair_cands(nemo_ctx *ctx, uint32_t *out, uint64_t cap, uint64_t *n_out);
+
 /* ---- lineage-driven cut search: minimal cuts up to size 8 from surviving derivations ----
  * The subject (a raw loaded graph g = 2r + cond), the candidates, dead_F(v), the
  * roots, "the outcome is lost under F", "cut" and "minimal" are nemo_min_cuts'

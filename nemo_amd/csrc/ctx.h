@@ -28,6 +28,7 @@
 #include "nearest_host.h"
 #include "node.h"
 #include "pairs_host.h"
+#include "repair_host.h"
 #include "stage_host.h"
 #include "wit_host.h"
 
@@ -361,6 +362,30 @@ struct CorpusState : GraphSizes {
   DevBuf<uint32_t> d_cutscan;        // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
   DevBuf<uint32_t> d_cutrows;        // [rows][4] nemo_cut
 
+  // minimal repair sets (k_repair.hip): the two calls' own state, void after the next of them or a load; independent
+  // of every other call's state.  One group d_rp*, which grows only inside the two calls, each buffer to the largest
+  // request so far, behind a wait for the stream: d_rpcnt, d_rptab and d_rphreg before anything is counted (the last
+  // two: the pair form alone); d_rpbits and d_rpcand together once the graph is known (the pair form's list has room
+  // for every node); d_rplive, d_rpw[0] and d_rpdead together once the candidates are counted, in this order; d_rpw[1],
+  // d_rpw[2] and d_rpscan together once round 1 has left the live list; d_rprows alone once the totals are known
+  bool rp_done = false;
+  uint64_t rp_rows = 0;              // rows of the last call (in nemo_ctx::h_repair)
+  uint64_t rp_stats[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // status, |A|, then per size: live candidates, hypotheses, minimal repairs
+  std::vector<uint32_t> rp_cand;     // the last call's candidates (nodes)
+  std::vector<uint32_t> rp_live;     // ... its upload: [K1] live positions | [K1] their nodes,
+  std::vector<uint64_t> rp_bits;     // ... the explicit form's bitmap,
+  nemo::LabTab rp_tab{};             // ... and the pair form's table
+  DevBuf<uint32_t> d_rpcnt;          // [2] the pair form's (absent sinks, Kahn levels)
+  DevBuf<nemo::LabTab> d_rptab;      // [1] the table k_lab_hash fills (the pair form, other != run 0)
+  DevBuf<uint32_t> d_rphreg;         // ... and its slots
+  DevBuf<uint64_t> d_rpbits;         // [repair::bitmap_words(V)] the absent bitmap
+  DevBuf<uint32_t> d_rpcand;         // [K] candidate position -> node (the pair form: room for V)
+  DevBuf<uint32_t> d_rplive;         // [K] live position -> candidate position | [K] live position -> node
+  DevBuf<uint64_t> d_rpw[3];         // the rounds' words, one per chunk of 64 ranks; [0]: round 0's word behind round 1's
+  DevBuf<uint64_t> d_rpdead;         // k_repair_glob: dead words of every workgroup of the launch
+  DevBuf<uint32_t> d_rpscan;         // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
+  DevBuf<uint32_t> d_rprows;         // [rows][4] nemo_repair
+
   // knock-out by label (k_klabel.hip): the call's own state, void after the next nemo_knockout_labels or load;
   // independent of knock-out, cut, diff, nearest and class state.  The eight buffers grow as one group, only
   // inside nemo_knockout_labels, each to the largest request so far, behind a wait for the stream, in this order
@@ -581,12 +606,13 @@ struct nemo_ctx {
   hipEvent_t ev_wit = nullptr;     // the witness calls' level counts / rows have reached pinned memory
   hipEvent_t ev_lin = nullptr;     // nemo_lineage_cuts' counts / candidates / a level's counters / the cuts have reached pinned memory
   hipEvent_t ev_lgc = nullptr;     // nemo_lineage_group_cuts' level counts / a level's counters / the cuts have reached pinned memory
-  hipEvent_t *const events[27] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_repair = nullptr;  // the repair calls' counts / rounds 0 and 1's words / totals / rows have reached pinned memory
+  hipEvent_t *const events[28] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
                                   &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts,
-                                  &ev_wit,     &ev_lin,     &ev_lgc};
+                                  &ev_wit,     &ev_lin,     &ev_lgc,     &ev_repair};
   // ... and the slices' (ev_state, ev_ready), destroyed with them
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
@@ -607,13 +633,15 @@ struct nemo_ctx {
   Pinned<uint32_t> h_wit;    // the witness calls: the level counts; then the rows
   Pinned<uint64_t> h_lin;    // nemo_lineage_cuts: the level counts, the counts and candidates, a level's counters; then the cuts' keys
   Pinned<uint64_t> h_lgc;    // nemo_lineage_group_cuts: the level counts, a level's counters; then the cuts' keys and lost counts
-  void **const pinned[30] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint32_t> h_repair;  // the repair calls: counts, rounds 0 and 1's words and the candidates, the totals, then the rows
+  void **const pinned[31] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
                              h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot(),
-                             h_gcuts.slot(),  h_wit.slot(),    h_lin.slot(),   h_lgc.slot()};
+                             h_gcuts.slot(),  h_wit.slot(),    h_lin.slot(),   h_lgc.slot(),
+                             h_repair.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

@@ -205,6 +205,23 @@ void launch_cut_glob(const DevCorpus &c, const CutArgs &a, uint32_t grid, hipStr
 void launch_cut_count(const CutArgs &a, hipStream_t s);  // a.scan[k] = popcount(a.words[k]), a.scan[n_chunks] = 0
 void launch_cut_emit(const CutArgs &a, hipStream_t s);   // the rows of the round's set bits at a.rows, by a.scan
 
+// One round of nemo_min_repair_sets / nemo_min_repairs (k_repair.hip): a round of CutArgs read as "repair" (bit t of
+// word k: restoring hypothesis 64 k + t's nodes lets the outcome hold; round 3: and none of its pairs does), over
+// the absent bitmap.  c.size 0 is round 0: one chunk of two hypotheses, S = {} and S = every candidate.
+struct RepairArgs {
+  CutArgs c;
+  const uint64_t *absent;   // [repair::bitmap_words(V)] bit v: node v is assumed lost; the bits past V are 0
+  uint32_t n_cand;          // round 0: the candidates c.cand[0 .. n_cand)
+};
+// the workgroups of round `size`'s (0..3) k_repair_lds resident on the device at lds_bytes of dynamic LDS (0: the query failed)
+uint32_t repair_lds_resident(uint32_t size, uint32_t lds_bytes, uint32_t n_cu);
+void launch_repair_lds(const DevCorpus &c, const RepairArgs &a, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void launch_repair_glob(const DevCorpus &c, const RepairArgs &a, uint32_t grid, hipStream_t s);
+// k_repair_absent: graph's sink goals whose label misses the table (key, mask: LabTab's layout), in node order at
+// cand[0 .. V) and as the bitmap `absent`; cnt[0] = how many, cnt[1] = the graph's Kahn levels
+void launch_repair_absent(const DevCorpus &c, uint32_t graph, const uint32_t *key, uint32_t mask, uint64_t *absent, uint32_t *cand,
+                          uint32_t *cnt, hipStream_t s);
+
 // One nemo_knockout_labels call (k_klabel.hip): hypotheses are label sets in chunks of 64, shared by every listed
 // graph; table c (c < n_chunks) maps a label to the mask of chunk c's sets that name it, table n_chunks is the
 // union filter of all named labels (klabel_host.h: key = label + 1, 0 empty, linear probing).

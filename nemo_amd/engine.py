@@ -42,6 +42,8 @@ NEAREST_DTYPE = np.dtype([("cand", np.uint32), ("dist", np.uint32), ("only_query
 KNOCK_DTYPE = np.dtype([("graph", np.uint32), ("node", np.uint32), ("n_dead", np.uint32), ("roots_dead", np.uint32),
                         ("n_roots", np.uint32)])
 KO_MASKS = 1  # NEMO_KO_MASKS
+# nemo_fetch_min_repair_stats' out[0] (NEMO_REPAIR_*)
+REPAIR_HOLDS, REPAIR_SEARCHED, REPAIR_BEYOND = 0, 1, 2
 # struct nemo_cut (nemo_fetch_min_cuts)
 CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (3,))])
 KL_SINKS = 1  # NEMO_KL_SINKS
@@ -135,6 +137,11 @@ def lib():
             "nemo_min_cuts": ([vp, u32, i32, vp, sz, u32, u32], i32),
             "nemo_fetch_min_cuts": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_min_cut_stats": ([vp, vp], i32),
+            "nemo_min_repair_sets": ([vp, u32, i32, vp, sz, vp, sz, u32, u32], i32),
+            "nemo_min_repairs": ([vp, u32, u32, u32, u32], i32),
+            "nemo_fetch_min_repairs": ([vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_min_repair_stats": ([vp, vp], i32),
+            "nemo_fetch_min_repair_cands": ([vp, vp, u64, P(u64)], i32),
             "nemo_lineage_cuts": ([vp, u32, i32, vp, sz, u32, u32], i32),
             "nemo_fetch_lineage_cuts": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_lineage_cut_stats": ([vp, vp], i32),
@@ -245,6 +252,20 @@ def witness_support(corpus: Corpus, g: int, mask: np.ndarray):
         if not rule[v] and not ch[v]:
             lab = int(corpus.label[n0 + v])
             out.append((v, lab, corpus.labels[lab] if corpus.labels is not None and lab < len(corpus.labels) else None))
+    return out
+
+
+def repair_labels(corpus: Corpus, g: int, rows: np.ndarray) -> List[List[str]]:
+    """The rows of Engine.min_repairs / min_repair_sets on graph g as label strings, for a report: per row the labels
+    of its nodes in row order (the label id as a string where the corpus keeps no string table)."""
+    n0 = int(corpus.node_off[g])
+    out = []
+    for row in np.asarray(rows, dtype=np.uint32).reshape(-1, 4).tolist():
+        labs = []
+        for v in row[1:1 + row[0]]:
+            lab = int(corpus.label[n0 + v])
+            labs.append(corpus.labels[lab] if corpus.labels is not None and lab < len(corpus.labels) else str(lab))
+        out.append(labs)
     return out
 
 
@@ -512,6 +533,50 @@ class Engine:
         out = np.zeros(9, np.uint64)
         self._chk(self.L.nemo_fetch_min_cut_stats(self.h, _p(out)))
         return out.reshape(3, 3)
+
+    def min_repairs(self, base: int, other: int, max_size: int = 2) -> np.ndarray:
+        """nemo_min_repairs: all minimal repairs of size <= max_size (1..3) of run `base`'s post graph, where the absent
+        set and the candidates are its sink goals whose label is no goal label of run `other`'s post graph (made on the
+        device; min_repair_stats() returns the list).  Returns the rows as an (n, 4) u32 array: size, then the nodes in
+        candidate-list order, unused entries UINT32_MAX, sorted by (size, colex rank of the live positions)."""
+        self._chk(self.L.nemo_min_repairs(self.h, int(base), int(other), int(max_size), 0))
+        return self.min_repair_rows()
+
+    def min_repair_sets(self, iteration: int, cond: int, absent: Sequence[int], candidates: Optional[Sequence[int]] = None,
+                        max_size: int = 2) -> np.ndarray:
+        """nemo_min_repair_sets: the same over an absent set and candidates the caller names (graph-local node indices
+        of any kind; candidates None: the absent list, in its order).  A repair is a set S of candidates such that
+        the outcome is not lost under absent \\ S."""
+        ab = np.ascontiguousarray(absent, dtype=np.uint32)
+        keep_a = ab if len(ab) else np.zeros(1, np.uint32)  # an empty list is a list: never NULL
+        if candidates is None:
+            self._chk(self.L.nemo_min_repair_sets(self.h, int(iteration), int(cond), _p(keep_a), len(ab), None, 0, int(max_size), 0))
+        else:
+            cand = np.ascontiguousarray(candidates, dtype=np.uint32)
+            keep_c = cand if len(cand) else np.zeros(1, np.uint32)
+            self._chk(self.L.nemo_min_repair_sets(self.h, int(iteration), int(cond), _p(keep_a), len(ab), _p(keep_c), len(cand),
+                                                  int(max_size), 0))
+        return self.min_repair_rows()
+
+    def min_repair_rows(self) -> np.ndarray:
+        """nemo_fetch_min_repairs: the rows of the last min_repairs / min_repair_sets call, (n, 4) u32."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_min_repairs(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.uint32)
+        self._chk(self.L.nemo_fetch_min_repairs(self.h, _p(out), len(out), ctypes.byref(n)))
+        return out
+
+    def min_repair_stats(self):
+        """nemo_fetch_min_repair_stats and nemo_fetch_min_repair_cands: (status, |A|, a 3 x 3 u64 array whose row s - 1 is
+        (live candidates entering round s, hypotheses evaluated, minimal repairs found), the candidate list the call
+        used as a u32 array).  status is REPAIR_HOLDS, REPAIR_SEARCHED or REPAIR_BEYOND."""
+        st = np.zeros(11, np.uint64)
+        self._chk(self.L.nemo_fetch_min_repair_stats(self.h, _p(st)))
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_min_repair_cands(self.h, None, 0, ctypes.byref(n)))
+        cand = np.zeros(n.value, np.uint32)
+        self._chk(self.L.nemo_fetch_min_repair_cands(self.h, _p(cand), len(cand), ctypes.byref(n)))
+        return int(st[0]), int(st[1]), st[2:].reshape(3, 3), cand
 
     def lineage_cuts(self, iteration: int, cond: int, candidates: Optional[Sequence[int]] = None, max_size: int = 3) -> np.ndarray:
         """nemo_lineage_cuts: all minimal cuts of size <= max_size (1..8) of a run's pre (cond 0) or post (cond 1) graph

@@ -13,6 +13,11 @@ size-1 cut, must be exactly the size-2 rows of the cut call, in order.  Reported
   us_per_chunk   the sweep kernel's time per chunk of 64 hypotheses
 With a library that has no nemo_min_cuts (an older build), only the sets path runs, so the same file measures the
 yardstick on it.  One JSON line.  Needs a GPU (no fallback).
+
+--repairs times the dual search instead of the sets path, beside nemo_min_cuts on the same graph: nemo_min_repair_sets
+with every sink goal of run 0's post graph absent and a candidate (K singles, C(K1,2) pairs: nemo_min_cuts' hypothesis
+counts where no single sink is a cut or a repair), kernels k_repair_lds / k_repair_glob, group k_repair; and the pair
+form nemo_min_repairs of run 0 against the first failed run, whose absent sinks are few.
 """
 import argparse
 import json
@@ -64,12 +69,44 @@ def report(wall, ms, group, kernels, chunks):
             "chunks": int(chunks), "us_per_chunk": round(1e3 * kern / max(int(chunks), 1), 5)}
 
 
+def repairs_mode(eng, corpus, it, a, out):
+    """nemo_min_cuts and nemo_min_repair_sets over all sink goals of run 0's post graph, max_size 2, and the pair form"""
+    cand = eng.knockout_leaves([it], 1)["node"].astype(np.uint32).copy()
+    eng.min_cuts(it, 1, None, 2)
+    cs = eng.min_cut_stats()
+    chunks = sum((int(cs[s][1]) + 63) // 64 for s in range(2))
+    wall, ms = timed_calls(eng, lambda: eng._chk(eng.L.nemo_min_cuts(eng.h, it, 1, None, 0, 2, 0)),
+                           ["k_cuts", "k_cut_lds", "k_cut_glob"], a.steps, a.warmup)
+    out["min_cuts"] = report(wall, ms, "k_cuts", ["k_cut_lds", "k_cut_glob"], chunks)
+    out["min_cuts"]["hypotheses"] = [int(cs[0][1]), int(cs[1][1])]
+    rows = eng.min_repair_sets(it, 1, cand, None, 2)
+    status, n_absent, rs, _ = eng.min_repair_stats()
+    chunks = 1 + sum((int(rs[s][1]) + 63) // 64 for s in range(2))  # round 0 is one chunk
+    wall, ms = timed_calls(eng, lambda: eng._chk(eng.L.nemo_min_repair_sets(eng.h, it, 1, cand.ctypes.data, len(cand), None, 0, 2, 0)),
+                           ["k_repair", "k_repair_lds", "k_repair_glob"], a.steps, a.warmup)
+    out["min_repair_sets"] = report(wall, ms, "k_repair", ["k_repair_lds", "k_repair_glob"], chunks)
+    out["min_repair_sets"].update({"status": status, "absent": n_absent, "rows": len(rows), "hypotheses": [int(rs[0][1]), int(rs[1][1])]})
+    if out["min_cuts"]["us_per_chunk"]:
+        out["repair_over_cut_per_chunk"] = round(out["min_repair_sets"]["us_per_chunk"] / out["min_cuts"]["us_per_chunk"], 4)
+    failed = corpus.failed_iters()
+    if failed:
+        eng.mark()
+        f = failed[0]
+        rows = eng.min_repairs(it, f, 2)
+        status, n_absent, rs, _ = eng.min_repair_stats()
+        wall, ms = timed_calls(eng, lambda: eng._chk(eng.L.nemo_min_repairs(eng.h, it, f, 2, 0)),
+                               ["k_repair", "k_repair_lds", "k_repair_glob", "k_repair_absent", "k_lab_hash"], a.steps, a.warmup)
+        out["min_repairs"] = {"other": f, "status": status, "absent": n_absent, "rows": len(rows),
+                              "wall_ms": round(statistics.median(wall), 3), "ms": {k: round(v, 4) for k, v in ms.items()}}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--lds-max", type=int, default=-1, help="option knock_lds_max (0: the global tier)")
+    ap.add_argument("--repairs", action="store_true", help="nemo_min_repair_sets / nemo_min_repairs beside nemo_min_cuts")
     a = ap.parse_args()
     have_cuts = hasattr(E.Engine, "min_cuts")
     corpus, _ = synth.generate(a.runs, prepend_run0=True, threads=min(16, os.cpu_count() or 1), **synth.CONFIGS["c3"])
@@ -79,6 +116,10 @@ def main() -> None:
     try:
         eng.set_option("knock_lds_max", a.lds_max)
         eng.load(corpus)
+        if a.repairs:
+            repairs_mode(eng, corpus, it, a, out)
+            print(json.dumps(out))
+            return
         leaves = eng.knockout_leaves([it], 1).copy()
         cand = leaves["node"].astype(np.uint32)
         single = (leaves["n_roots"] > 0) & (leaves["roots_dead"] == leaves["n_roots"])
