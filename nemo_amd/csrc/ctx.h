@@ -126,6 +126,24 @@ struct LinBufs {
   DevBuf<uint32_t> ctab;           // the cuts' table: lin::table_slots(cap)
 };
 
+// The buffers and the result of a search of sets of size <= 3 over one graph (cut_api.h's node_search): nemo_min_cuts
+// keeps one group, the two repair calls share another.  Each buffer grows only inside its calls, to the largest
+// request so far, behind a wait for the stream: cand by the call, which fills it before the search starts; live, w[0]
+// and dead together once the candidates are counted, in this order; w[1], w[2] and scan together once round 1 has
+// left the live list; rows alone once the totals are known.
+struct CutBufs {
+  DevBuf<uint32_t> cand;           // [K] candidate position -> node
+  DevBuf<uint32_t> live;           // [K] live position -> candidate position | [K] live position -> node
+  DevBuf<uint64_t> w[3];           // the rounds' words, one per chunk of 64 ranks
+  DevBuf<uint64_t> dead;           // the global tier: dead words of every workgroup of the launch
+  DevBuf<uint32_t> scan;           // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
+  DevBuf<uint32_t> rows;           // [rows][4] nemo_cut / nemo_repair
+  std::vector<uint32_t> h_cand;    // the last call's candidates (nodes)
+  std::vector<uint32_t> h_live;    // ... and its upload: [K1] live positions | [K1] their nodes
+  uint64_t n_rows = 0;             // rows of the last call (in the call's pinned buffer)
+  bool done = false;
+};
+
 // Graph g = nodes [node_off[g], node_off[g + 1]), edges likewise; run r's graphs are 2r (pre) and 2r + 1 (post).
 struct GraphSizes {
   std::vector<uint64_t> node_off, edge_off;
@@ -344,47 +362,26 @@ struct CorpusState : GraphSizes {
   DevBuf<uint64_t> d_kodead;         // dead words of the chunks that keep them (knock::Chunk::moff)
 
   // minimal cut sets (k_cuts.hip): the call's own state, void after the next nemo_min_cuts or load; independent of
-  // knock-out, diff, nearest and class state.  All of it grows only inside nemo_min_cuts, each buffer to the largest
-  // request so far, behind a wait for the stream: d_cutdesc alone, before anything is counted; d_cutcand, d_cutlive,
-  // d_cutw[0] and d_cutdead together once the candidates are known, in this order; d_cutw[1], d_cutw[2] and
-  // d_cutscan together once round 1 has left the live list; d_cutrows alone once the totals are known
-  bool cut_done = false;
-  uint64_t cut_rows = 0;             // rows of the last call (in nemo_ctx::h_cuts)
+  // knock-out, diff, nearest and class state.  d_cutdesc grows alone inside nemo_min_cuts, behind a wait for the
+  // stream, before anything is counted; cut.cand alone once the candidates are counted; the rest as CutBufs states
+  CutBufs cut;                       // the search's (rows in nemo_ctx::h_cuts)
   uint64_t cut_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size: live candidates, hypotheses, minimal cuts
   uint32_t cut_up[4] = {0, 0, 0, 0};  // the last call's uploads to d_cutdesc
-  std::vector<uint32_t> cut_cand;    // the last call's candidates (nodes)
-  std::vector<uint32_t> cut_live;    // ... and its upload: [K1] live positions | [K1] their nodes
   DevBuf<uint32_t> d_cutdesc;        // [8] k_ko_leaves' list, offsets and counts for the one graph (cand == NULL)
-  DevBuf<uint32_t> d_cutcand;        // [K] candidate position -> node
-  DevBuf<uint32_t> d_cutlive;        // [K] live position -> candidate position | [K] live position -> node
-  DevBuf<uint64_t> d_cutw[3];        // the rounds' words, one per chunk of 64 ranks
-  DevBuf<uint64_t> d_cutdead;        // k_cut_glob: dead words of every workgroup of the launch
-  DevBuf<uint32_t> d_cutscan;        // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
-  DevBuf<uint32_t> d_cutrows;        // [rows][4] nemo_cut
 
   // minimal repair sets (k_repair.hip): the two calls' own state, void after the next of them or a load; independent
-  // of every other call's state.  One group d_rp*, which grows only inside the two calls, each buffer to the largest
-  // request so far, behind a wait for the stream: d_rpcnt, d_rptab and d_rphreg before anything is counted (the last
-  // two: the pair form alone); d_rpbits and d_rpcand together once the graph is known (the pair form's list has room
-  // for every node); d_rplive, d_rpw[0] and d_rpdead together once the candidates are counted, in this order; d_rpw[1],
-  // d_rpw[2] and d_rpscan together once round 1 has left the live list; d_rprows alone once the totals are known
-  bool rp_done = false;
-  uint64_t rp_rows = 0;              // rows of the last call (in nemo_ctx::h_repair)
+  // of every other call's state.  Each buffer grows only inside the two calls, to the largest request so far, behind a
+  // wait for the stream: d_rpcnt, d_rptab and d_rphreg before anything is counted (the last two: the pair form alone);
+  // d_rpbits and rp.cand together once the graph is known (the pair form's list has room for every node); the rest as
+  // CutBufs states
+  CutBufs rp;                        // the search's (rows in nemo_ctx::h_repair); w[0]: round 0's word behind round 1's
   uint64_t rp_stats[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // status, |A|, then per size: live candidates, hypotheses, minimal repairs
-  std::vector<uint32_t> rp_cand;     // the last call's candidates (nodes)
-  std::vector<uint32_t> rp_live;     // ... its upload: [K1] live positions | [K1] their nodes,
-  std::vector<uint64_t> rp_bits;     // ... the explicit form's bitmap,
+  std::vector<uint64_t> rp_bits;     // the last call's bitmap (the explicit form)
   nemo::LabTab rp_tab{};             // ... and the pair form's table
   DevBuf<uint32_t> d_rpcnt;          // [2] the pair form's (absent sinks, Kahn levels)
   DevBuf<nemo::LabTab> d_rptab;      // [1] the table k_lab_hash fills (the pair form, other != run 0)
   DevBuf<uint32_t> d_rphreg;         // ... and its slots
   DevBuf<uint64_t> d_rpbits;         // [repair::bitmap_words(V)] the absent bitmap
-  DevBuf<uint32_t> d_rpcand;         // [K] candidate position -> node (the pair form: room for V)
-  DevBuf<uint32_t> d_rplive;         // [K] live position -> candidate position | [K] live position -> node
-  DevBuf<uint64_t> d_rpw[3];         // the rounds' words, one per chunk of 64 ranks; [0]: round 0's word behind round 1's
-  DevBuf<uint64_t> d_rpdead;         // k_repair_glob: dead words of every workgroup of the launch
-  DevBuf<uint32_t> d_rpscan;         // per round [chunks + 1] popcounts -> first rows; then the scan's tile sums
-  DevBuf<uint32_t> d_rprows;         // [rows][4] nemo_repair
 
   // knock-out by label (k_klabel.hip): the call's own state, void after the next nemo_knockout_labels or load;
   // independent of knock-out, cut, diff, nearest and class state.  The eight buffers grow as one group, only

@@ -1,8 +1,9 @@
 // cut_host.h — the arithmetic of nemo_min_cuts (k_cuts.hip; DESIGN.md §Minimal cut sets) as pure functions: the
 // colex rank of a pair / triple of live positions and its inverse (the kernels call the very same code), the
 // round-3 test for a cut pair inside a triple (k_cuts.hip and k_lcuts.hip call the very same code), the per-round
-// limit, the validation of the candidate list, the live list from round 1's words, and the chunk and
-// grid counts.  No HIP and no context, so tools/cut_host_check.cpp drives it under the host sanitizers.
+// limit, the validation of the candidate list, the live list from round 1's words, the chunk and grid counts, and
+// the sizes cut_api.h's node_search takes (the global tier's resident bound, the bound of a round's hypotheses, round
+// 1's words and pinned elements).  No HIP and no context, so tools/cut_host_check.cpp drives it under the host sanitizers.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -123,5 +124,24 @@ static inline uint32_t grid(uint64_t n_chunks, uint64_t resident, uint32_t cap) 
   if (cap) g = std::min<uint64_t>(g, cap);
   return (uint32_t)std::max<uint64_t>(g, 1);
 }
+
+// ---- the sizes of a search over one graph (cut_api.h's node_search) ---------------------------------------
+// The global tier's resident workgroups, untuned: two per CU, fewer where their dead words (dead_words u64 each)
+// would pass CUT_DEAD_BYTES all together; at least one.
+static inline uint64_t glob_resident(uint32_t n_cu, uint64_t dead_words) {
+  return std::max<uint64_t>(1, std::min<uint64_t>(2ull * n_cu, CUT_DEAD_BYTES / (8 * std::max<uint64_t>(dead_words, 1))));
+}
+
+// An upper bound of any round's hypotheses over K candidates, before the live list is known; at least one.
+static inline uint64_t most_hyps(uint64_t K, uint32_t max_size) {
+  uint64_t most = std::max<uint64_t>(K, 1);
+  for (uint32_t sz = 2; sz <= max_size; sz++) most = std::max(most, std::min<uint64_t>(round_hyps(K, sz), CUT_MAX_HYPS));
+  return most;
+}
+
+// Round 1's words, with round 0's one word behind them where the search has a round 0; and the u32 elements of the
+// pinned buffer that takes those words, the K candidates behind them and the call's 8 counts.
+static inline uint64_t first_words(uint64_t K, bool round0) { return chunks(K) + (round0 ? 1 : 0); }
+static inline uint64_t first_pinned(uint64_t K, bool round0) { return 2 * first_words(K, round0) + K + 8; }
 
 }  // namespace cuts

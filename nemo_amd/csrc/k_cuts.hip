@@ -1,59 +1,20 @@
 // k_cuts.hip — nemo_min_cuts (DESIGN.md §Minimal cut sets): all minimal cuts of size <= 3 of a raw provenance
 // graph read as an AND/OR circuit.  A round's hypotheses are the sets of 1, 2 or 3 live candidates in colex rank
 // order (cut_host.h), so a workgroup makes the seeds of a chunk of 64 hypotheses from the chunk's index alone.
-// k_cut_lds is the persistent form of k_ko_lds: it stages the graph's LDS image once and loops over chunks,
-// running the knock-out sweep on each; a chunk's result is one word, the AND of the root words (the zeroing, the
-// sweep and the lost word: ko_sweep.h; round 3's cut-pair test: cut_host.h).
+// k_cut_lds is the persistent form of k_ko_lds: it stages the graph's LDS image once and runs cut_dev.h's loop over
+// the round's chunks, the knock-out sweep on each; a chunk's result is one word, the AND of the root words.
 // k_cut_glob is the same loop over the CSR in device memory.  k_cut_count / k_cut_emit turn the rounds' words
-// into nemo_cut rows in (size, rank) order.
-#include "cut_host.h"
-#include "device.h"
-#include "internal.h"
-#include "ko_sweep.h"
+// into nemo_cut rows in (size, rank) order (the repair searches' rows too).
+#include "cut_dev.h"
 
 namespace nemo {
-
-// All chunks ci = blockIdx.x, += gridDim.x of the round on a graph whose image is in place.  All 256 threads.
-template <bool LDS, uint32_t SIZE>
-__device__ __forceinline__ void cut_loop(const CutArgs &a, const KoImg<LDS> &g) {
-  __shared__ uint64_t s_and[KO_BLOCK / 64];
-  const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-  uint64_t *dead = g.dead;
-  for (uint32_t ci = blockIdx.x; ci < a.n_chunks; ci += gridDim.x) {
-    // the previous chunk's words go (its last reads lie behind the barrier that ends the loop body)
-    ko_zero_dead<LDS>(g);
-    const uint32_t first = ci * KO_CHUNK, n = min(KO_CHUNK, a.n_hyp - first);
-    // seeds: lane t's hypothesis is the set of rank first + t; hypotheses of one chunk share nodes
-    bool sub = false;  // round 3: one of the set's pairs is a cut already
-    if (tid < n) {
-      const uint64_t h = (uint64_t)first + tid, bit = 1ull << tid;
-      const cuts::Pos p = cuts::unrank<SIZE>(h);  // the round is a template parameter: no divergent unrank paths
-      unsigned long long *d64 = reinterpret_cast<unsigned long long *>(dead);
-      const uint32_t va = a.lnode[p.a], vb = SIZE >= 2u ? a.lnode[p.b] : g.V, vc = SIZE >= 3u ? a.lnode[p.c] : g.V;
-      if (va < g.V) atomicOr(&d64[va], (unsigned long long)bit);
-      if (SIZE >= 2u && vb < g.V) atomicOr(&d64[vb], (unsigned long long)bit);
-      if (SIZE >= 3u && vc < g.V) atomicOr(&d64[vc], (unsigned long long)bit);
-      if (SIZE == 3u) sub = cuts::has_cut_pair(a.pairs, p);  // round 2's words, read while the sweep runs
-    }
-    if (!LDS) __threadfence_block();
-    __syncthreads();
-    ko_sweep<LDS>(g);
-    // lost: every root dead, per bit column.  Every thread holds the word; wave 0, whose lanes hold the chunk's
-    // `sub`, finishes.  (s_and is written next behind the next chunk's barriers.)
-    uint64_t lost = ko_lost_word<LDS>(g, n, s_and);
-    if (wave == 0) {
-      if (SIZE == 3u) lost &= ~__ballot(sub);
-      if (lane == 0) a.words[ci] = lost;
-    }
-  }
-}
 
 // one instantiation per round (SIZE = 1, 2, 3)
 template <uint32_t SIZE>
 __global__ __launch_bounds__(KO_BLOCK) void k_cut_lds(DevCorpus c, CutArgs a) {
   extern __shared__ __align__(16) uint8_t dyn[];
   const KoImg<true> g = ko_stage_image(c.view(a.graph), dyn);  // once; the loop's first barrier ends the staging
-  cut_loop<true, SIZE>(a, g);
+  cut_loop<true, SIZE, false>(a, g, nullptr, 0u);
 }
 
 // the workgroup's own dead words in a.dead; a fence and a barrier per level, as k_ko_glob.  Correct, not tuned.
@@ -61,7 +22,7 @@ template <uint32_t SIZE>
 __global__ __launch_bounds__(KO_BLOCK) void k_cut_glob(DevCorpus c, CutArgs a) {
   const GraphView gv = c.view(a.graph);
   const KoImg<false> g = ko_glob_image(gv, a.dead + (uint64_t)blockIdx.x * (((uint64_t)gv.V + 1ull) & ~1ull));
-  cut_loop<false, SIZE>(a, g);
+  cut_loop<false, SIZE, false>(a, g, nullptr, 0u);
 }
 
 // ---- the rows -------------------------------------------------------------------------------------

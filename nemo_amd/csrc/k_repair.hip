@@ -1,79 +1,12 @@
 // k_repair.hip — nemo_min_repair_sets / nemo_min_repairs (DESIGN.md §Minimal repair sets): all minimal repairs of
-// size <= 3 of a raw provenance graph under an absent set A.  The monotone dual of k_cuts.hip: a chunk's dead words
-// start from A's bitmap (all 64 columns set on an absent node) where cut_loop starts from zeros, and a hypothesis
-// clears its column on the nodes it restores where a cut sets it.  The hypotheses, their colex ranks and round 3's
-// pair test are cut_host.h's; the image, the sweep and the lost word are ko_sweep.h's, unchanged.  A chunk's result
-// word is the complement of its lost word.  k_repair_lds / k_repair_glob are persistent, one instantiation per
-// round; round 0 is one chunk of two hypotheses, S = {} and S = every candidate.  The rows come from k_cuts.hip's
-// k_cut_count / k_cut_emit.  k_repair_absent makes the pair form's absent set and candidate list.
-#include "cut_host.h"
-#include "device.h"
-#include "internal.h"
-#include "ko_sweep.h"
+// size <= 3 of a raw provenance graph under an absent set A.  The monotone dual of k_cuts.hip, by the same loop in
+// its repair mode (cut_dev.h).  k_repair_lds / k_repair_glob are persistent, one instantiation per round; round 0 is
+// one chunk of two hypotheses, S = {} and S = every candidate.  The rows come from k_cuts.hip's k_cut_count /
+// k_cut_emit.  k_repair_absent makes the pair form's absent set and candidate list.
+#include "cut_dev.h"
 #include "repair_host.h"
 
 namespace nemo {
-
-// dead[v] = absent(v) ? ~0 : 0 where ko_zero_dead writes zeros: the same whole 16-byte pairs, the same fence and
-// barrier behind them.  A pair's two nodes 2 i and 2 i + 1 lie in one word of the bitmap; the bits past V are 0, so
-// an odd V's padding word stays 0.  The caller's last reads of the words lie behind a barrier, and so does the
-// staging of the bitmap.  All 256 threads.
-template <bool LDS>
-__device__ __forceinline__ void repair_fill(const KoImg<LDS> &g, const uint64_t *absent) {
-  uint4 *z = reinterpret_cast<uint4 *>(g.dead);
-  const uint32_t pairs = (g.V + 1u) / 2u;
-  for (uint32_t i = threadIdx.x; i < pairs; i += KO_BLOCK) {
-    const uint32_t v = 2u * i;
-    const uint32_t two = (uint32_t)(absent[v >> 6] >> (v & 63u)) & 3u;
-    const uint32_t lo = (two & 1u) ? ~0u : 0u, hi = (two & 2u) ? ~0u : 0u;
-    z[i] = make_uint4(lo, lo, hi, hi);
-  }
-  if (!LDS) __threadfence_block();
-  __syncthreads();
-}
-
-// All chunks ci = blockIdx.x, += gridDim.x of the round on a graph whose image and bitmap are in place.  All 256 threads.
-template <bool LDS, uint32_t SIZE>
-__device__ __forceinline__ void repair_loop(const RepairArgs &ra, const KoImg<LDS> &g, const uint64_t *absent) {
-  __shared__ uint64_t s_and[KO_BLOCK / 64];
-  const CutArgs &a = ra.c;
-  const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-  unsigned long long *d64 = reinterpret_cast<unsigned long long *>(g.dead);
-  for (uint32_t ci = blockIdx.x; ci < a.n_chunks; ci += gridDim.x) {
-    // the previous chunk's words go (its last reads lie behind the barrier that ends the loop body)
-    repair_fill<LDS>(g, absent);
-    const uint32_t first = ci * KO_CHUNK, n = min(KO_CHUNK, a.n_hyp - first);
-    bool sub = false;  // round 3: one of the set's pairs is a repair already
-    if (SIZE == 0u) {
-      // column 0 restores nothing; column 1 restores every candidate (distinct nodes; atomic as the other rounds')
-      for (uint32_t k = tid; k < ra.n_cand; k += KO_BLOCK) {
-        const uint32_t v = a.cand[k];
-        if (v < g.V) atomicAnd(&d64[v], ~2ull);
-      }
-    } else if (tid < n) {
-      // seeds: lane t's hypothesis is the set of rank first + t; hypotheses of one chunk share nodes
-      const uint64_t h = (uint64_t)first + tid;
-      const unsigned long long keep = ~(1ull << tid);
-      const cuts::Pos p = cuts::unrank<(SIZE ? SIZE : 1u)>(h);
-      const uint32_t va = a.lnode[p.a], vb = SIZE >= 2u ? a.lnode[p.b] : g.V, vc = SIZE >= 3u ? a.lnode[p.c] : g.V;
-      if (va < g.V) atomicAnd(&d64[va], keep);
-      if (SIZE >= 2u && vb < g.V) atomicAnd(&d64[vb], keep);
-      if (SIZE >= 3u && vc < g.V) atomicAnd(&d64[vc], keep);
-      if (SIZE == 3u) sub = cuts::has_cut_pair(a.pairs, p);  // round 2's words, read while the sweep runs
-    }
-    if (!LDS) __threadfence_block();
-    __syncthreads();
-    ko_sweep<LDS>(g);
-    // holds: some root alive, per bit column.  Every thread holds the lost word; wave 0, whose lanes hold the
-    // chunk's `sub`, finishes.  (s_and is written next behind the next chunk's barriers.)
-    const uint64_t lost = ko_lost_word<LDS>(g, n, s_and);
-    if (wave == 0) {
-      uint64_t holds = ~lost & (n == KO_CHUNK ? ~0ull : (1ull << n) - 1ull);
-      if (SIZE == 3u) holds &= ~__ballot(sub);
-      if (lane == 0) a.words[ci] = holds;
-    }
-  }
-}
 
 // one instantiation per round (SIZE = 0, 1, 2, 3).  The bitmap is staged once behind k_ko_lds's image
 // (repair::repair_lds_bytes); the barrier behind it also ends the image's staging.
@@ -88,7 +21,7 @@ __global__ __launch_bounds__(KO_BLOCK) void k_repair_lds(DevCorpus c, RepairArgs
   const uint32_t n4 = (uint32_t)(repair::bitmap_words(gv.V) / 2u);
   for (uint32_t i = threadIdx.x; i < n4; i += KO_BLOCK) dst[i] = src[i];
   __syncthreads();
-  repair_loop<true, SIZE>(a, g, absent);
+  cut_loop<true, SIZE, true>(a.c, g, absent, a.n_cand);
 }
 
 // the workgroup's own dead words in a.c.dead, the bitmap read where it lies; a fence and a barrier per level, as
@@ -97,7 +30,7 @@ template <uint32_t SIZE>
 __global__ __launch_bounds__(KO_BLOCK) void k_repair_glob(DevCorpus c, RepairArgs a) {
   const GraphView gv = c.view(a.c.graph);
   const KoImg<false> g = ko_glob_image(gv, a.c.dead + (uint64_t)blockIdx.x * (((uint64_t)gv.V + 1ull) & ~1ull));
-  repair_loop<false, SIZE>(a, g, a.absent);
+  cut_loop<false, SIZE, true>(a.c, g, a.absent, a.n_cand);
 }
 
 // ---- the pair form's absent set -----------------------------------------------------------------------

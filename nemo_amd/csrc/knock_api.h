@@ -1,8 +1,9 @@
 // knock_api.h — the host code the knock-out family's calls share (api_knock.hip, api_cuts.hip, api_klabel.hip,
 // api_lcuts.hip, api_gcuts.hip, api_witness.hip): the wait for a call's copies to pinned memory, the dynamic LDS of a persistent
 // LDS-tier launch, the listed graphs' split into the two tiers (api_klabel.hip, api_lcuts.hip, api_gcuts.hip), and the
-// rounds' sizes and the rows of the three cut searches (api_cuts.hip, api_lcuts.hip, api_gcuts.hip), and the rounds'
-// limits, launch plans and driver of the two searches by label (api_lcuts.hip, api_gcuts.hip).  Every call keeps
+// rounds' sizes and the rows of the cut and repair searches (cut_api.h for api_cuts.hip and api_repair.hip;
+// api_lcuts.hip, api_gcuts.hip), and the rounds' limits, launch plans and driver of the two searches by label
+// (api_lcuts.hip, api_gcuts.hip).  The searches over one graph share more: cut_api.h.  Every call keeps
 // its own event, pinned buffer, device buffers and state (ctx.h); nothing here owns any.  GroupTimer and grow_group
 // are ctx.h's.
 #pragma once

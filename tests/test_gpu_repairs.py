@@ -552,6 +552,87 @@ def test_buffers_grow_and_are_reused(eng, edges_corpus):
     check(eng, corpus, len(leaves) - 2, leaves[-2], None, 3, "a second, larger call")
 
 
+def groups_of(sizes):
+    """goal 0 <- rule 1 <- one goal per group, each <- one rule per leaf <- its leaf: the leaves of one group are a
+    cut, one leaf of every group is a repair.  Returns the graph and the groups' leaves."""
+    kinds, edges, groups = "gr", [(0, 1)], []
+    for n in sizes:
+        top = len(kinds)
+        kinds += "g" + "rg" * n
+        edges += [(1, top)] + [e for k in range(n) for e in ((top, top + 1 + 2 * k), (top + 1 + 2 * k, top + 2 + 2 * k))]
+        groups.append([top + 2 + 2 * k for k in range(n)])
+    return (kinds, edges), groups
+
+
+# 12 sink goals each: 66 pairs (two chunks, the second of 2) and 220 triples (four chunks, the last of 28).  MIXED has a
+# pair repair and triple repairs and no cut of size <= 3; GROUPS has a pair cut, two triple cuts and no repair of size <= 3.
+GROUPS = groups_of([2, 3, 3, 4])
+
+
+@pytest.mark.parametrize("lds, grid", [(-1, 0), (0, 0), (-1, 1), (0, 1)])
+def test_cut_and_repair_calls_interleaved(lds, grid):
+    """nemo_min_cuts and the two repair calls share their search driver and their sweep loop: on one engine, in turn,
+    each call's rows, stats and candidates are those of the same call on a fresh engine.  Both tiers; cut_grid 1: one
+    workgroup walks every chunk of a round, so both modes refill the dead words between chunks."""
+    from tests.test_gpu_min_cuts import expected as cuts_expected, got_rows as cut_rows
+    corpus = build([MIXED[0], GROUPS[0], HAND[0]])
+    mixed, flat = MIXED[1], [v for grp in GROUPS[1] for v in grp]
+    g_mixed, g_groups = Graph(corpus, 1), Graph(corpus, 3)
+    assert len(mixed) == 12 and g_groups.leaves == flat and len(flat) == 12
+    # the shapes, by the references: 12 live candidates in every call, a round 3 that drops sets over a found pair
+    want_cut = cuts_expected(g_groups, flat, 3)
+    assert [r[0] for r in want_cut[0]] == [2, 3, 3] and want_cut[1] == [[12, 12, 0], [12, 66, 1], [12, 220, 2]]
+    assert cuts_expected(g_mixed, mixed, 3) == ([], [[12, 12, 0], [12, 66, 0], [12, 220, 0]])
+    want_rep = expected(g_mixed, mixed, None, 3)
+    assert want_rep[0] == SEARCHED and want_rep[3][1] == [12, 66, 1] and want_rep[3][2][:2] == [12, 220] and want_rep[3][2][2] >= 1
+    want_pair = expected(g_groups, flat, None, 3)  # every label is its own: the absent sinks are all sinks
+    assert want_pair[0] == SEARCHED and want_pair[2] == [] and want_pair[3][2] == [12, 220, 0]
+    order = mixed[::-1]
+    want_list = expected(g_mixed, mixed, order, 3)
+    assert want_list[2] and want_list[2] != want_rep[2]
+
+    def cuts_call(it):
+        def call(e):
+            rows = cut_rows(e.min_cuts(it, 1, None, 3))
+            assert rows == cut_rows(e.min_cut_rows())
+            return rows, e.min_cut_stats().tolist()
+        return call
+
+    def repair_result(e, arr):
+        st = e.min_repair_stats()
+        assert got_rows(e.min_repair_rows()) == got_rows(arr)
+        return int(st[0]), int(st[1]), got_rows(arr), st[2].tolist(), st[3].tolist()
+
+    calls = [("nemo_min_cuts, the groups", cuts_call(1), (want_cut[0], want_cut[1])),
+             ("nemo_min_repair_sets", lambda e: repair_result(e, e.min_repair_sets(0, 1, mixed, None, 3)), want_rep),
+             ("nemo_min_cuts, another graph", cuts_call(0), ([], [[12, 12, 0], [12, 66, 0], [12, 220, 0]])),
+             ("nemo_min_repairs", lambda e: repair_result(e, e.min_repairs(1, 0, 3)), want_pair),
+             ("nemo_min_repair_sets, a candidate list", lambda e: repair_result(e, e.min_repair_sets(0, 1, mixed, order, 3)), want_list)]
+
+    def engine():
+        e = E.Engine(0)
+        e.set_option("knock_lds_max", lds)
+        e.set_option("cut_grid", grid)
+        e.load(corpus)
+        e.mark()
+        return e
+
+    one = engine()
+    try:
+        for what, call, want in calls:
+            got = call(one)
+            fresh = engine()
+            try:
+                alone = call(fresh)
+            finally:
+                fresh.close()
+            print(f"{what} (knock_lds_max {lds}, cut_grid {grid}): {got[:-1]}")
+            assert got == alone, f"{what}: the interleaved call differs from the same call on a fresh engine"
+            assert tuple(got) == tuple(want), f"{what}: differs from the reference"
+    finally:
+        one.close()
+
+
 def test_other_results_are_left_alone(eng):
     from tests.small import random_corpus
     corpus = random_corpus(1000, n_runs=6, max_nodes=40)[0]

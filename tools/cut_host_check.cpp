@@ -1,7 +1,8 @@
 // cut_host_check — drives the host side of nemo_min_cuts (nemo_amd/csrc/cut_host.h): unrank(rank(x)) == x for
 // every pair and triple of up to 200 positions, ranks monotone and dense in colex order, the ranks around
 // 2^32 - 2 (2,953 live candidates give 4,287,437,076 triples, which just fits; 2,955 do not), the per-round limit
-// from both sides, round 3's cut-pair test against brute force for every triple of 9 positions, every outcome of the candidate validation, the live list and the chunk and grid counts.
+// from both sides, round 3's cut-pair test against brute force for every triple of 9 positions, every outcome of the candidate validation, the live list, the chunk and grid counts,
+// and the sizes of a search over one graph (the global tier's resident bound, the bound of a round's hypotheses, round 1's words and pinned elements) at small values and at each bound's edge.
 // Meant for the host sanitizers; it calls nothing on a device:
 //   g++ -std=c++17 -g -Wall -fsanitize=address,undefined -static-libasan -static-libubsan
 //       tools/cut_host_check.cpp -o tools/cut_host_check
@@ -173,7 +174,29 @@ static void check_live_and_grid() {
   CHECK(cuts::grid(2, 512, 3) == 2 && cuts::grid(0, 512, 0) == 1 && cuts::grid(10, 0, 0) == 1);
 }
 
+// the sizes node_search takes: small values and each bound's edge
+static void check_search_sizes() {
+  // 256 CUs: two workgroups each until 512 of them would keep more than CUT_DEAD_BYTES, that is past 2^18 dead words
+  CHECK(cuts::glob_resident(256, 0) == 512 && cuts::glob_resident(256, 2) == 512 && cuts::glob_resident(1, 2) == 2);
+  CHECK(cuts::glob_resident(256, 1ull << 18) == 512 && cuts::glob_resident(256, (1ull << 18) + 2) == 511);
+  CHECK(cuts::glob_resident(256, 1ull << 19) == 256 && cuts::glob_resident(256, 1ull << 26) == 2);
+  CHECK(cuts::glob_resident(256, 1ull << 27) == 1 && cuts::glob_resident(256, (1ull << 27) + 2) == 1);  // never none
+  CHECK(cuts::glob_resident(0, 2) == 1 && cuts::glob_resident(256, ~0ull >> 3) == 1);
+  CHECK(cuts::most_hyps(0, 1) == 1 && cuts::most_hyps(0, 3) == 1 && cuts::most_hyps(1, 3) == 1 && cuts::most_hyps(2, 3) == 2);
+  CHECK(cuts::most_hyps(5, 1) == 5 && cuts::most_hyps(5, 2) == 10 && cuts::most_hyps(5, 3) == 10 && cuts::most_hyps(10, 3) == 120);
+  CHECK(cuts::most_hyps(12, 2) == 66 && cuts::most_hyps(3, 2) == 3 && cuts::most_hyps(3, 3) == 3);
+  // a K at which round_hyps passes CUT_MAX_HYPS: the bound stays there
+  CHECK(cuts::most_hyps(2954, 3) == 4291795704ull && cuts::most_hyps(2955, 3) == CUT_MAX_HYPS && cuts::most_hyps(2955, 2) == cuts::choose2(2955));
+  CHECK(cuts::most_hyps(92682, 2) == 4294930221ull && cuts::most_hyps(92683, 2) == CUT_MAX_HYPS && cuts::most_hyps(92683, 1) == 92683);
+  CHECK(cuts::most_hyps(2642246, 3) == CUT_MAX_HYPS);  // choose3 saturates
+  CHECK(cuts::first_words(0, false) == 0 && cuts::first_words(0, true) == 1 && cuts::first_words(64, false) == 1);
+  CHECK(cuts::first_words(64, true) == 2 && cuts::first_words(65, false) == 2 && cuts::first_words(65, true) == 3);
+  CHECK(cuts::first_pinned(0, false) == 8 && cuts::first_pinned(0, true) == 10);
+  CHECK(cuts::first_pinned(65, false) == 2 * 2 + 65 + 8 && cuts::first_pinned(65, true) == 2 * 3 + 65 + 8);
+}
+
 int main() {
+  check_search_sizes();
   check_small();
   check_large();
   check_cut_pair();
