@@ -1324,6 +1324,93 @@ func (n *Neo4J) MinRepairs(base, other uint, maxSize uint) (*RepairResult, error
 	return res, nil
 }
 
+// LineageRepairResult is what LineageRepairs and LineageRepairSets return.
+type LineageRepairResult struct {
+	Status     uint64     // C.NEMO_REPAIR_HOLDS, C.NEMO_REPAIR_SEARCHED or C.NEMO_REPAIR_BEYOND
+	Absent     uint64     // the size of the absent set
+	Stats      [18]uint64 // per size 0..8: sets evaluated, minimal repairs found
+	Candidates []uint32   // candidate position -> node
+	Repairs    []*MinRepair
+}
+
+// lineageRepairResult fetches the result of the last lineage repair call on
+// the graph p (stats, candidates, rows).
+func (n *Neo4J) lineageRepairResult(p *provGraph) (*LineageRepairResult, error) {
+	var stats [20]uint64
+	if err := n.err(C.nemo_fetch_lineage_repair_stats(n.ctx, (*C.uint64_t)(unsafe.Pointer(&stats[0])))); err != nil {
+		return nil, err
+	}
+	res := &LineageRepairResult{Status: stats[0], Absent: stats[1]}
+	copy(res.Stats[:], stats[2:])
+	var cnt C.uint64_t
+	if err := n.err(C.nemo_fetch_lineage_repair_cands(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	cands := make([]C.uint32_t, cnt+1) // never empty: &cands[0] below
+	if err := n.err(C.nemo_fetch_lineage_repair_cands(n.ctx, &cands[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	for _, v := range cands[:cnt] {
+		res.Candidates = append(res.Candidates, uint32(v))
+	}
+	if err := n.err(C.nemo_fetch_lineage_repairs(n.ctx, nil, 0, &cnt)); err != nil {
+		return nil, err
+	}
+	reps := make([]C.nemo_lineage_repair, cnt+1)
+	if err := n.err(C.nemo_fetch_lineage_repairs(n.ctx, &reps[0], cnt, &cnt)); err != nil {
+		return nil, err
+	}
+	for _, rep := range reps[:cnt] {
+		m := &MinRepair{}
+		for j := 0; j < int(rep.size); j++ {
+			v := uint32(rep.node[j])
+			id, label := "", ""
+			if int(v) < len(p.goals) {
+				id, label = p.goals[v].ID, p.goals[v].Label
+			}
+			m.Nodes, m.IDs, m.Labels = append(m.Nodes, v), append(m.IDs, id), append(m.Labels, label)
+		}
+		res.Repairs = append(res.Repairs, m)
+	}
+	return res, nil
+}
+
+// LineageRepairs returns all minimal repairs of at most maxSize (1..8) base
+// events of run base's post provenance against run other
+// (nemo_lineage_repairs), as MinRepairs does up to size 3, by the dual of the
+// search LineageCuts makes: a restore set that does not bring the outcome back
+// is extended only by the missing events that lie in its blocker, the proof
+// that every root is still dead.  The repairs come sorted by size, then by the
+// colex order of their positions in the candidate list.
+func (n *Neo4J) LineageRepairs(base, other uint, maxSize uint) (*LineageRepairResult, error) {
+	if err := n.err(C.nemo_lineage_repairs(n.ctx, C.uint32_t(base), C.uint32_t(other), C.uint32_t(maxSize), 0)); err != nil {
+		return nil, err
+	}
+	return n.lineageRepairResult(n.graphs[2*n.runIdx[base]+1])
+}
+
+// LineageRepairSets is LineageRepairs over an absent set and candidates the
+// caller names, local node indices of one run's pre or post provenance
+// (nemo_lineage_repair_sets); candidates nil means the absent list itself.
+func (n *Neo4J) LineageRepairSets(iter uint, cond string, absent []uint32, candidates []uint32, maxSize uint) (*LineageRepairResult, error) {
+	lost := make([]C.uint32_t, len(absent)+1) // never empty: &lost[0] below
+	for i, v := range absent {
+		lost[i] = C.uint32_t(v)
+	}
+	var list *C.uint32_t
+	if candidates != nil {
+		nodes := make([]C.uint32_t, len(candidates)+1)
+		for i, v := range candidates {
+			nodes[i] = C.uint32_t(v)
+		}
+		list = &nodes[0]
+	}
+	if err := n.err(C.nemo_lineage_repair_sets(n.ctx, C.uint32_t(iter), condIndex(cond), &lost[0], C.size_t(len(absent)), list, C.size_t(len(candidates)), C.uint32_t(maxSize), 0)); err != nil {
+		return nil, err
+	}
+	return n.lineageRepairResult(n.graphs[2*n.runIdx[iter]+int(condIndex(cond))])
+}
+
 // FailureClass is one distinct failure mode among the failed runs: the runs
 // whose differential provenance against the good run is the same graph.
 type FailureClass struct {

@@ -266,6 +266,7 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       into few ranges; the tier is "knock_lds_max"'s;
  *                       nemo_min_label_cuts' and nemo_min_group_cuts' sweeps take the
  *                       same cap
+ *                       (the lineage cut and lineage repair searches' sweeps as well)
  *   "kl_hitlist"        1 (default, also -1): the LDS-tier sweep of nemo_knockout_labels
  *                       lists, once per graph, the nodes whose label some set names,
  *                       and a chunk of 64 sets probes its table with those alone.  0:
@@ -282,12 +283,14 @@ int nemo_set_stream(nemo_ctx *ctx, void *stream);
  *                       device memory; -1 = the default); takes effect at the
  *                       next witness call; the grid cap is "kl_grid"'s;
  *                       nemo_lineage_cuts takes its tier from the same option
+ *                       (the lineage repair calls too: their image is 8 V bytes larger)
  *   "lineage_children_max"  most children one level of nemo_lineage_cuts may emit,
  *                       counted before duplicates are removed (default 2^24 =
  *                       16777216: 16 bytes per child gives 256 MiB, a memory bound,
  *                       not a tuned number; at least 64, at most 2^31; -1 = the
  *                       default); a level past it fails the call with
- *                       NEMO_ERR_LIMIT                                            */
+ *                       NEMO_ERR_LIMIT
+ *                       (the lineage repair calls' levels are held to the same limit) */
 int nemo_set_option(nemo_ctx *ctx, const char *name, int64_t value);
 /* Record a hipEvent pair around every launch (per-kernel timing, see nemo_timings). */
 int nemo_set_timing(nemo_ctx *ctx, int enable);
@@ -698,6 +701,92 @@ int nemo_fetch_min_repairs(nemo_ctx *ctx, nemo_repair *out, uint64_t cap, uint64
 int nemo_fetch_min_repair_stats(nemo_ctx *ctx, uint64_t out[11]);
 /* out[p] = the node of candidate position p; out == NULL queries *n_out.       */
 int nemo_fetch_min_repair_cands(nemo_ctx *ctx, uint32_t *out, uint64_t cap, uint64_t *n_out);
+
+/* ---- lineage repair search: minimal repairs up to size 8 from blockers ----
+ * The dual of nemo_lineage_cuts, as nemo_min_repair_sets is the dual of
+ * nemo_min_cuts.  The subject (a raw loaded graph g = 2r + cond), dead_F(v), the
+ * roots, "the outcome is lost under F", the absent set A, cand within A,
+ * F = A \ S, "repair", "minimal" and the three statuses are nemo_min_repair_sets'
+ * definitions above, unchanged.
+ * Blocker.  Let F be a removed set under which the outcome is lost (every root is
+ * dead and there is a root).  blame_F is defined top-down along the DUETO edges,
+ * roots first, by the node's own kind only: every root is blamed; a blamed node
+ * that is in F blames nothing further; a blamed rule not in F blames exactly one
+ * child, its dead child of smallest node index (the forward rows ascend, so that
+ * is the first dead child in row order); a blamed goal not in F blames every
+ * child (it has children and all are dead, or it would be alive).
+ * B_F = {v : blame_F(v)}; every blamed node is dead under F.
+ * Lemma.  If F' contains the part of B_F in F, every node of B_F is dead under F' (bottom-up
+ * inside B_F: a blamed node of F is in F'; a blamed rule outside F has its blamed
+ * child dead; a blamed goal outside F has every child blamed and dead), hence
+ * the outcome is lost under F'.  So a repair R that contains S must restore a
+ * node of the blocker: it contains a node of B_{A \ S} that is in cand \ S.
+ * Result, whatever the search below does: all minimal repairs of size
+ * <= max_size.  The rows are sorted by (size, colex order of the candidate
+ * positions, largest position first); a row's nodes ascend by candidate position,
+ * unused entries UINT32_MAX.  For max_size <= 3 the rows, the status, |A| and
+ * the candidate list are nemo_min_repair_sets' / nemo_min_repairs' own, in their
+ * order.
+ * Status: decided as round 0 of nemo_min_repair_sets decides it, from S = {} and
+ * S = cand, before the levels.  NEMO_REPAIR_HOLDS and NEMO_REPAIR_BEYOND give
+ * zero rows and every level stat is 0; under NEMO_REPAIR_SEARCHED level 0 reports
+ * 1 set evaluated and 0 found.
+ * Search (specified, so that the stats are deterministic): the hitting-set tree
+ * over blockers, level by level.  Level 0 evaluates S = {}.  Level d evaluates a
+ * frontier of distinct sets of d candidate positions; a set under which the
+ * outcome holds is a minimal repair of size d and is not expanded.  For every
+ * other set S the children are S + {e} for every candidate e in B_{A \ S} with e
+ * not in S.  The frontier of level d + 1 holds the distinct children that have no
+ * proper subset among the repairs of sizes <= d.  The search stops after level
+ * max_size, or at an empty frontier.  Every minimal repair is reached: a minimal
+ * repair R and a non-repair S inside it meet in the blocker of A \ S outside S
+ * (the lemma), so some child of S lies in R; a reached repair that is not minimal
+ * holds a smaller minimal repair found at an earlier level and was filtered
+ * before it was evaluated.  A non-repair whose blocker holds no candidate outside
+ * S has no children: nothing above it is a repair.
+ * nemo_lineage_repair_sets: the caller names both lists, graph-local node indices
+ * of any kind.  NEMO_ERR_INVALID, checked on the host in this order before
+ * anything is uploaded, with nemo_min_repair_sets' messages under this call's
+ * name: cond outside 0 / 1; max_size outside 1..8 or flags != 0 ("max_size must
+ * be 1..8"); an absent node >= V_g; an absent node listed twice; a candidate
+ * listed twice; a candidate that is not in absent.  cand == NULL means
+ * cand = absent, in its order.  More than 65535 candidates is NEMO_ERR_LIMIT (a
+ * set is kept as eight u16 candidate positions): the explicit list, the implicit
+ * list, and the pair form's device-made list once its count is known.
+ * nemo_lineage_repairs: the pair form.  A = cand = the sink goals of the base
+ * run's raw post graph whose label is no goal label of the other run's post
+ * graph, in node-index order, made on the device as nemo_min_repairs makes them;
+ * it needs what that call needs (NEMO_ERR_STATE before nemo_mark_holds).
+ * An empty A, a graph without roots and (x, x) give NEMO_REPAIR_HOLDS, as the
+ * exhaustive calls do.  An iteration that is not loaded is NEMO_ERR_NOTFOUND; a
+ * node context and a call with no corpus loaded return NEMO_ERR_STATE.
+ * Limits, NEMO_ERR_LIMIT, the call then leaves no results: nemo_lineage_cuts': a
+ * frontier of more than 2^32 - 2 sets; a level that emits more children (counted
+ * before duplicates are removed) than the option "lineage_children_max" allows.
+ * A level that counted more children than the emission buffer holds runs again,
+ * once, behind a buffer of the counted size; its repairs are not appended twice.
+ * The calls block until the rows are on the host.  The results are the two calls'
+ * own state: valid until the next of them or nemo_load_corpus (the fetches return
+ * NEMO_ERR_STATE otherwise), independent of every other call's state in both
+ * directions, nemo_lineage_cuts' and the exhaustive repair calls' included.  No
+ * option of its own: the tier is "wit_lds_max"'s (the image is the witness calls'
+ * plus a third u64 word per node and the absent bitmap), the grid cap
+ * "kl_grid"'s, the emission limit "lineage_children_max"'s.                      */
+typedef struct nemo_lineage_repair {
+  uint32_t size;    /* 1..8                                                          */
+  uint32_t node[8]; /* nodes in candidate-list order, unused = UINT32_MAX            */
+} nemo_lineage_repair; /* nemo_lineage_cut's layout                                 */
+int nemo_lineage_repair_sets(nemo_ctx *ctx, uint32_t iteration, int cond, const uint32_t *absent, size_t n_absent,
+                             const uint32_t *cand, size_t n_cand, uint32_t max_size, uint32_t flags);
+int nemo_lineage_repairs(nemo_ctx *ctx, uint32_t base_iter, uint32_t other_iter, uint32_t max_size, uint32_t flags);
+/* out[k] for every minimal repair k; out == NULL queries *n_out.               */
+int nemo_fetch_lineage_repairs(nemo_ctx *ctx, nemo_lineage_repair *out, uint64_t cap, uint64_t *n_out);
+/* out[0]: the status; out[1]: |A|; per size d = 0..8: out[2 + 2 d] = sets evaluated
+ * at size d, out[3 + 2 d] = minimal repairs found of size d (zeros past the last
+ * level the search reached, and all 18 zero unless NEMO_REPAIR_SEARCHED).       */
+int nemo_fetch_lineage_repair_stats(nemo_ctx *ctx, uint64_t out[20]);
+/* out[p] = the node of candidate position p; out == NULL queries *n_out.       */
+int nemo_fetch_lineage_repair_cands(nemo_ctx *ctx, uint32_t *out, uint64_t cap, uint64_t *n_out);
 
 /* ---- lineage-driven cut search: minimal cuts up to size 8 from surviving derivations ----
  * The subject (a raw loaded graph g = 2r + cond), the candidates, dead_F(v), the

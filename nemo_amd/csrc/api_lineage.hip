@@ -6,6 +6,22 @@
 // level runs again behind a grown emission buffer.
 #include "knock_api.h"
 #include "lin_api.h"
+#include "lin_run.h"
+
+// lin_run.h: the level loop and the keys' way to the host for a search in a translation unit of its own
+int lin_levels_run(nemo_ctx *c, const LinRun &r, double *bytes, double *ops, uint64_t *n_found) {
+  auto prepare = [](uint32_t, uint64_t, uint64_t) { return NEMO_OK; };
+  return lin_levels(c, r.who, r.shorten, *r.bufs, *r.h, r.ev, *r.a, r.K, r.max_size, r.stats, nullptr, r.level_limit, prepare, r.evaluate,
+                    r.emit_bound, bytes, ops, n_found);
+}
+
+int lin_sorted_run(nemo_ctx *c, const LinBufs &b, Pinned<uint64_t> &h, hipEvent_t ev, uint64_t n, std::vector<lin::Key> *keys,
+                   std::vector<uint32_t> *order) {
+  LinCuts cuts;
+  if (int rc = lin_sorted_keys(c, b, nullptr, h, ev, n, &cuts)) return rc;
+  keys->swap(cuts.keys), order->swap(cuts.order);
+  return NEMO_OK;
+}
 
 namespace {
 

@@ -23,6 +23,7 @@
 #include "klabel_host.h"
 #include "lcut_host.h"
 #include "lin_host.h"
+#include "lrep_host.h"
 #include "knock_host.h"
 #include "lgc_host.h"
 #include "nearest_host.h"
@@ -509,6 +510,26 @@ struct CorpusState : GraphSizes {
   LinBufs d_lg;                      // the level loop's
   DevBuf<uint32_t> d_lgnl;           // [cap] the cuts' lost counts
 
+  // lineage repair search (k_lrepair.hip): the two calls' own state, void after the next nemo_lineage_repair_sets /
+  // nemo_lineage_repairs or load; independent of every other call's state (kl_nlev above is the load's, not a result).
+  // One group d_lr*, which grows only inside the two calls, each buffer to the largest request so far, behind a wait
+  // for the stream: d_lrcnt, d_lrtab and d_lrhreg before anything is counted (the pair form alone); d_lrbits and
+  // d_lrcand together once the graph is known (the pair form's list has room for every node); d_lr.ctr and d_lrreg
+  // together once the candidates are counted; the rest of d_lr as LinBufs states
+  bool lr_done = false;
+  uint64_t lr_stats[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // status, |A|, then per size 0..8: sets evaluated, minimal repairs
+  std::vector<nemo_lineage_repair> lr_rows;  // the last call's rows, sorted
+  std::vector<uint32_t> lr_cand;     // the last call's candidates (nodes)
+  std::vector<uint64_t> lr_bits;     // the last call's bitmap (the explicit form)
+  nemo::LabTab lr_tab{};             // ... and the pair form's table
+  DevBuf<uint32_t> d_lrcnt;          // [2] the pair form's (absent sinks, Kahn levels)
+  DevBuf<nemo::LabTab> d_lrtab;      // [1] the table k_lab_hash fills (the pair form, other != run 0)
+  DevBuf<uint32_t> d_lrhreg;         // ... and its slots
+  DevBuf<uint64_t> d_lrbits;         // [repair::bitmap_words(V)] the absent bitmap
+  DevBuf<uint32_t> d_lrcand;         // [K] candidate position -> node
+  DevBuf<uint64_t> d_lrreg;          // k_lrep_glob: dead, blame and stop-rule words of every workgroup of the launch
+  LinBufs d_lr;                      // the level loop's; ctr[3]: the two-hypothesis launch's lost word
+
   // pulls: per-slot (offset, count) and the region cursor come back to pinned
   // memory asynchronously; the first fetch waits for them
   int pull_which = -1;
@@ -604,12 +625,14 @@ struct nemo_ctx {
   hipEvent_t ev_lin = nullptr;     // nemo_lineage_cuts' counts / candidates / a level's counters / the cuts have reached pinned memory
   hipEvent_t ev_lgc = nullptr;     // nemo_lineage_group_cuts' level counts / a level's counters / the cuts have reached pinned memory
   hipEvent_t ev_repair = nullptr;  // the repair calls' counts / rounds 0 and 1's words / totals / rows have reached pinned memory
-  hipEvent_t *const events[28] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
+  hipEvent_t ev_lrep = nullptr;    // the lineage repair calls' counts / status word / a level's counters / the repairs have reached pinned memory
+  hipEvent_t *const events[29] = {&ev_fork,    &ev_pull,    &ev_trig,  &ev_protos, &ev_red,  &ev_diff,
                                   &ev_misc,    &ev_tiers,   &ev_up_hlab, &ev_up_succ, &ev_up_dsrc,
                                   &ev_copied,  &ev_simp,    &ev_auxpull, &ev_flags, &ev_stage,
                                   &ev_dclass,  &ev_near,    &ev_whole,   &ev_knock,
                                   &ev_cuts,    &ev_klabel,  &ev_lcuts,   &ev_gcuts,
-                                  &ev_wit,     &ev_lin,     &ev_lgc,     &ev_repair};
+                                  &ev_wit,     &ev_lin,     &ev_lgc,     &ev_repair,
+                                  &ev_lrep};
   // ... and the slices' (ev_state, ev_ready), destroyed with them
   std::vector<hipEvent_t> ev_up;  // one per upload part
 
@@ -631,14 +654,15 @@ struct nemo_ctx {
   Pinned<uint64_t> h_lin;    // nemo_lineage_cuts: the level counts, the counts and candidates, a level's counters; then the cuts' keys
   Pinned<uint64_t> h_lgc;    // nemo_lineage_group_cuts: the level counts, a level's counters; then the cuts' keys and lost counts
   Pinned<uint32_t> h_repair;  // the repair calls: counts, rounds 0 and 1's words and the candidates, the totals, then the rows
-  void **const pinned[31] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
+  Pinned<uint64_t> h_lrep;   // the lineage repair calls: the level counts, the counts and candidates, the status word, a level's counters; then the repairs' keys
+  void **const pinned[32] = {h_red.slot(),   h_tab.slot(),     h_nmiss.slot(), h_mrows.slot(), h_tpre.slot(),
                              h_tpost.slot(), h_tasync.slot(),  h_tcounts.slot(), h_tiers.slot(), h_mask.slot(),
                              h_succ.slot(),  h_flags.slot(),   h_hlab.slot(),  h_dsrc.slot(),  h_chht.slot(),
                              h_choff.slot(), h_pull.cnt.slot(), h_pull.off.slot(), h_pull.cur.slot(),
                              h_dcin.slot(),  h_dcout.slot(),   h_near.slot(),  h_knock.slot(),
                              h_cuts.slot(),  h_klabel.slot(), h_lcuts.slot(),
                              h_gcuts.slot(),  h_wit.slot(),    h_lin.slot(),   h_lgc.slot(),
-                             h_repair.slot()};
+                             h_repair.slot(),  h_lrep.slot()};
   // missing rows copied with the D masks: the last nemo_fetch_missing's count.  A size hint only
   // (a short one costs a second copy), kept across loads: batches of one shape find as many rows
   uint64_t mrows_hint = 256;

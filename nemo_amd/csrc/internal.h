@@ -404,6 +404,20 @@ void launch_lgc_lds(const DevCorpus &c, const LgcArgs &a, uint32_t grid, hipStre
 void launch_lgc_glob(const DevCorpus &c, const LgcArgs &a, uint32_t grid, hipStream_t s);
 void launch_lgc_cuts(const LgcArgs &a, hipStream_t s);
 
+// One level of nemo_lineage_repair_sets / nemo_lineage_repairs (k_lrepair.hip): the frontier's sets of candidate
+// positions, 64 per chunk, are evaluated on the one graph under the absent bitmap (k_lrep_lds / k_lrep_glob), which
+// appends the holding ones to the repairs and emits the children of the others; k_lin_filter and k_lin_rehash (on `l`)
+// make the next frontier and the repairs' table.  `l` is the level as nemo_lineage_cuts' kernels read it, with "cut"
+// read as "repair"; l.region holds three word arrays per workgroup (lrep_host.h).
+struct LrepArgs {
+  LinArgs l;
+  const uint64_t *absent;    // [repair::bitmap_words(V)] bit v: node v is assumed lost; the bits past V are 0
+  uint32_t status;           // 1: one workgroup, two hypotheses (S = {}, S = every candidate); l.ctr[3] = their lost word
+};
+uint32_t lrep_lds_resident(uint32_t lds_bytes, uint32_t n_cu);
+void launch_lrep_lds(const DevCorpus &c, const LrepArgs &a, uint32_t grid, hipStream_t s);  // a.l.lds_total bytes of LDS
+void launch_lrep_glob(const DevCorpus &c, const LrepArgs &a, uint32_t grid, hipStream_t s);
+
 // One nemo_diff_classes call (k_dclass.hip) over the D masks of the nu distinct label sources.
 struct DclassArgs {
   const uint8_t *mask;      // [n_entries][V0] D masks (the buffer ends on a 16-byte boundary)

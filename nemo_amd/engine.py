@@ -57,6 +57,8 @@ WITNESS_DTYPE = np.dtype([("graph", np.uint32), ("n_roots", np.uint32), ("roots_
 WIT_ALL, WIT_MASKS, WIT_SINKS = 1, 2, 4  # NEMO_WIT_ALL, NEMO_WIT_MASKS, NEMO_WIT_SINKS
 # struct nemo_lineage_cut (nemo_fetch_lineage_cuts)
 LINEAGE_CUT_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (8,))])
+# struct nemo_lineage_repair (nemo_fetch_lineage_repairs): nemo_lineage_cut's layout
+LINEAGE_REPAIR_DTYPE = np.dtype([("size", np.uint32), ("node", np.uint32, (8,))])
 # struct nemo_lineage_group_cut (nemo_fetch_lineage_group_cuts)
 LINEAGE_GROUP_CUT_DTYPE = np.dtype([("size", np.uint32), ("group", np.uint32, (8,))])
 
@@ -142,6 +144,11 @@ def lib():
             "nemo_fetch_min_repairs": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_min_repair_stats": ([vp, vp], i32),
             "nemo_fetch_min_repair_cands": ([vp, vp, u64, P(u64)], i32),
+            "nemo_lineage_repair_sets": ([vp, u32, i32, vp, sz, vp, sz, u32, u32], i32),
+            "nemo_lineage_repairs": ([vp, u32, u32, u32, u32], i32),
+            "nemo_fetch_lineage_repairs": ([vp, vp, u64, P(u64)], i32),
+            "nemo_fetch_lineage_repair_stats": ([vp, vp], i32),
+            "nemo_fetch_lineage_repair_cands": ([vp, vp, u64, P(u64)], i32),
             "nemo_lineage_cuts": ([vp, u32, i32, vp, sz, u32, u32], i32),
             "nemo_fetch_lineage_cuts": ([vp, vp, u64, P(u64)], i32),
             "nemo_fetch_lineage_cut_stats": ([vp, vp], i32),
@@ -577,6 +584,54 @@ class Engine:
         cand = np.zeros(n.value, np.uint32)
         self._chk(self.L.nemo_fetch_min_repair_cands(self.h, _p(cand), len(cand), ctypes.byref(n)))
         return int(st[0]), int(st[1]), st[2:].reshape(3, 3), cand
+
+    def lineage_repairs(self, base: int, other: int, max_size: int = 3) -> np.ndarray:
+        """nemo_lineage_repairs: all minimal repairs of size <= max_size (1..8) of run `base`'s post graph, where the
+        absent set and the candidates are its sink goals whose label is no goal label of run `other`'s post graph (as
+        min_repairs makes them; at most 65535), found by the lineage repair search: a restore set that does not bring
+        the outcome back is extended only by candidates that lie in its blocker.  Returns the rows as a structured array
+        (LINEAGE_REPAIR_DTYPE: size, node[8] ascending by candidate position, unused entries UINT32_MAX), sorted by
+        (size, colex order of the candidate positions); lineage_repair_stats() has the status and the levels' counts."""
+        self._chk(self.L.nemo_lineage_repairs(self.h, int(base), int(other), int(max_size), 0))
+        return self.lineage_repair_rows()
+
+    def lineage_repair_sets(self, iteration: int, cond: int, absent: Sequence[int], candidates: Optional[Sequence[int]] = None,
+                            max_size: int = 3) -> np.ndarray:
+        """nemo_lineage_repair_sets: the same over an absent set and candidates the caller names (as min_repair_sets
+        takes them; candidates None: the absent list, in its order)."""
+        ab = np.ascontiguousarray(absent, dtype=np.uint32)
+        keep_a = ab if len(ab) else np.zeros(1, np.uint32)  # an empty list is a list: never NULL
+        if candidates is None:
+            self._chk(self.L.nemo_lineage_repair_sets(self.h, int(iteration), int(cond), _p(keep_a), len(ab), None, 0, int(max_size), 0))
+        else:
+            cand = np.ascontiguousarray(candidates, dtype=np.uint32)
+            keep_c = cand if len(cand) else np.zeros(1, np.uint32)
+            self._chk(self.L.nemo_lineage_repair_sets(self.h, int(iteration), int(cond), _p(keep_a), len(ab), _p(keep_c), len(cand),
+                                                      int(max_size), 0))
+        return self.lineage_repair_rows()
+
+    def lineage_repair_rows(self) -> np.ndarray:
+        """nemo_fetch_lineage_repairs: the rows of the last lineage_repairs / lineage_repair_sets call."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_lineage_repairs(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, LINEAGE_REPAIR_DTYPE)
+        self._chk(self.L.nemo_fetch_lineage_repairs(self.h, _p(out), len(out), ctypes.byref(n)))
+        return out
+
+    def lineage_repair_stats(self):
+        """nemo_fetch_lineage_repair_stats: (status, |A|, a 9 x 2 u64 array, row d = (sets evaluated at size d, minimal
+        repairs found of size d), d = 0..8).  status is REPAIR_HOLDS, REPAIR_SEARCHED or REPAIR_BEYOND."""
+        st = np.zeros(20, np.uint64)
+        self._chk(self.L.nemo_fetch_lineage_repair_stats(self.h, _p(st)))
+        return int(st[0]), int(st[1]), st[2:].reshape(9, 2)
+
+    def lineage_repair_cands(self) -> np.ndarray:
+        """nemo_fetch_lineage_repair_cands: the candidate list the last call used (position -> node), a u32 array."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.nemo_fetch_lineage_repair_cands(self.h, None, 0, ctypes.byref(n)))
+        cand = np.zeros(n.value, np.uint32)
+        self._chk(self.L.nemo_fetch_lineage_repair_cands(self.h, _p(cand), len(cand), ctypes.byref(n)))
+        return cand
 
     def lineage_cuts(self, iteration: int, cond: int, candidates: Optional[Sequence[int]] = None, max_size: int = 3) -> np.ndarray:
         """nemo_lineage_cuts: all minimal cuts of size <= max_size (1..8) of a run's pre (cond 0) or post (cond 1) graph
