@@ -97,12 +97,12 @@ int nemo_min_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t *can
 
 int nemo_fetch_min_cuts(nemo_ctx *c, nemo_cut *out, uint64_t cap, uint64_t *n_out) {
   if (!c) return NEMO_ERR_INVALID;
-  return node_search_fetch(c, c->cs.cut, "nemo_fetch_min_cuts", "nemo_min_cuts", c->h_cuts.p, c->cs.cut.n_rows, sizeof(nemo_cut), out, cap, n_out);
+  return fetch_result(c, c->cs.cut.done, "nemo_fetch_min_cuts", "nemo_min_cuts", c->h_cuts.p, c->cs.cut.n_rows, sizeof(nemo_cut), out, cap, n_out);
 }
 
 int nemo_fetch_min_cut_stats(nemo_ctx *c, uint64_t out[9]) {
   if (!c || !out) return NEMO_ERR_INVALID;
-  return node_search_fetch(c, c->cs.cut, "nemo_fetch_min_cut_stats", "nemo_min_cuts", c->cs.cut_stats, 9, 8, out, 9, nullptr);
+  return fetch_result(c, c->cs.cut.done, "nemo_fetch_min_cut_stats", "nemo_min_cuts", c->cs.cut_stats, 9, 8, out, 9, nullptr);
 }
 
 }  // extern "C"

@@ -227,23 +227,16 @@ int nemo_lineage_group_cuts(nemo_ctx *c, const uint32_t *iters, size_t n, int co
 
 int nemo_fetch_lineage_group_cuts(nemo_ctx *c, nemo_lineage_group_cut *out, uint32_t *n_lost, uint64_t cap, uint64_t *n_out) {
   if (!c) return NEMO_ERR_INVALID;
-  if (c->node || !c->cs.lg_done)
-    return fail(c, NEMO_ERR_STATE, "nemo_fetch_lineage_group_cuts before nemo_lineage_group_cuts (or after a later nemo_load_corpus)");
-  const uint64_t n = c->cs.lg_rows.size();  // no ensure_whole: reads the last call's host rows, no graph
-  if (n_out) *n_out = n;
-  if (!out) return NEMO_OK;
-  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
-  if (n) memcpy(out, c->cs.lg_rows.data(), n * sizeof(nemo_lineage_group_cut));
-  if (n && n_lost) memcpy(n_lost, c->cs.lg_nlost.data(), n * sizeof(uint32_t));
-  return NEMO_OK;
+  const std::vector<nemo_lineage_group_cut> &rows = c->cs.lg_rows;
+  const int rc = fetch_result(c, c->cs.lg_done, "nemo_fetch_lineage_group_cuts", "nemo_lineage_group_cuts", rows.data(), rows.size(),
+                              sizeof(nemo_lineage_group_cut), out, cap, n_out);
+  if (rc == NEMO_OK && out && n_lost && !rows.empty()) memcpy(n_lost, c->cs.lg_nlost.data(), rows.size() * sizeof(uint32_t));  // the second column
+  return rc;
 }
 
 int nemo_fetch_lineage_group_cut_stats(nemo_ctx *c, uint64_t out[18]) {
   if (!c || !out) return NEMO_ERR_INVALID;
-  if (c->node || !c->cs.lg_done)
-    return fail(c, NEMO_ERR_STATE, "nemo_fetch_lineage_group_cut_stats before nemo_lineage_group_cuts (or after a later nemo_load_corpus)");
-  memcpy(out, c->cs.lg_stats, sizeof c->cs.lg_stats);
-  return NEMO_OK;
+  return fetch_result(c, c->cs.lg_done, "nemo_fetch_lineage_group_cut_stats", "nemo_lineage_group_cuts", c->cs.lg_stats, 18, 8, out, 18, nullptr);
 }
 
 }  // extern "C"

@@ -1,27 +1,13 @@
 // api_lineage.hip — nemo_lineage_cuts and its fetches (k_lineage.hip, lin_host.h; DESIGN.md §Lineage-driven cut
-// search).  The level counts, the tier rule and image (wit_host.h: the witness calls'), the launch's dynamic LDS, the
-// wait for the copies, the buffer group and the timing group are knock_api.h's and ctx.h's, shared with the knock-out
-// family.  The host drives the levels (lin_api.h's lin_levels, shared with nemo_lineage_group_cuts): per level it
-// queues the evaluation and the filter, reads one block of three counters from pinned memory, and decides whether the
-// level runs again behind a grown emission buffer.
+// search).  The level counts, the wait for the copies, the buffer group and the timing group are knock_api.h's and
+// ctx.h's, shared with the knock-out family; the tier rule and image are the witness calls' (wit_host.h).  The call
+// keeps its entry checks, its early ends and its candidate source (the caller's list, or the sink goals k_ko_leaves
+// lists); the search from there to the rows is lin_api.h's lin_node_search, shared with api_lrepair.hip: the host
+// drives the levels (lin_levels, shared with nemo_lineage_group_cuts too), per level it queues the evaluation and the
+// filter, reads one block of three counters from pinned memory, and decides whether the level runs again behind a
+// grown emission buffer.
 #include "knock_api.h"
 #include "lin_api.h"
-#include "lin_run.h"
-
-// lin_run.h: the level loop and the keys' way to the host for a search in a translation unit of its own
-int lin_levels_run(nemo_ctx *c, const LinRun &r, double *bytes, double *ops, uint64_t *n_found) {
-  auto prepare = [](uint32_t, uint64_t, uint64_t) { return NEMO_OK; };
-  return lin_levels(c, r.who, r.shorten, *r.bufs, *r.h, r.ev, *r.a, r.K, r.max_size, r.stats, nullptr, r.level_limit, prepare, r.evaluate,
-                    r.emit_bound, bytes, ops, n_found);
-}
-
-int lin_sorted_run(nemo_ctx *c, const LinBufs &b, Pinned<uint64_t> &h, hipEvent_t ev, uint64_t n, std::vector<lin::Key> *keys,
-                   std::vector<uint32_t> *order) {
-  LinCuts cuts;
-  if (int rc = lin_sorted_keys(c, b, nullptr, h, ev, n, &cuts)) return rc;
-  keys->swap(cuts.keys), order->swap(cuts.order);
-  return NEMO_OK;
-}
 
 namespace {
 
@@ -56,7 +42,7 @@ int nemo_lineage_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t 
   uint32_t r;
   if ((rc = run_index(c, iteration, &r))) return rc;
   const uint32_t g = 2 * r + (uint32_t)cond;
-  const uint64_t V = cs.nv(g), E = cs.ne(g);
+  const uint64_t V = cs.nv(g);
   if (cand) {
     size_t where = 0;
     switch (lin::check_cands(cand, n_cand, V, &where)) {
@@ -80,7 +66,7 @@ int nemo_lineage_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t 
   if (L == 0) return lin_empty(cs);
   if ((rc = c->h_lin.grow(c, 8))) return rc;
   GroupTimer timer(c, "k_lineage");
-  double bytes = 0, ops = 0;
+  double bytes = 0;
   if ((rc = grow_drop(c, cs.d_lndesc, 8))) return rc;
   // cand == NULL: the graph's sink goals, counted by k_ko_leaves
   uint32_t *desc = cs.d_lndesc.p;  // [0] the graph | [1..2] offsets 0, K | [4..5] (sink goals, Kahn levels)
@@ -100,19 +86,9 @@ int nemo_lineage_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t 
       return fail(c, NEMO_ERR_LIMIT, "nemo_lineage_cuts: %llu sink goals exceed 65535 candidates (a set is eight u16 candidate positions): pass a list",
                   (unsigned long long)K);
   }
-  // the tier and the grid: as many workgroups as are resident, at most one per chunk
-  const bool lds = wit::lds_fits(V, E, L, c->opt.wit_lds_max);
-  const uint32_t image = lds ? wit::wit_lds_bytes((uint32_t)V, (uint32_t)E, L) : 0u;
-  const uint64_t rw = lds ? 0 : wit::glob_words(V);
-  uint32_t lds_total = 0, res_lds = 1;
-  if (lds && (rc = ko_lds_total(c, who, "k_lin_lds", [&](uint32_t b) { return nemo::lin_lds_resident(b, cs.dc.n_cu); }, image, 0, 4096,
-                                &lds_total, &res_lds)))
-    return rc;
-  const uint32_t cap = c->opt.kl_grid;
-  const uint64_t resident = lds ? res_lds : klabel::region_grid(2ull * cs.dc.n_cu, rw);
-  {
-    const uint64_t need[3] = {std::max<uint64_t>(K, 1), 4, std::max<uint64_t>(1, rw * lin::grid(~0ull, resident, cap))};
-    if ((rc = grow_group(c, need, cs.d_lncand, cs.d_ln.ctr, cs.d_lnreg))) return rc;
+  {  // the candidates on the device
+    const uint64_t need = std::max<uint64_t>(K, 1);
+    if ((rc = grow_group(c, &need, cs.d_lncand))) return rc;
   }
   if (cand) {
     cs.lin_cand.assign(cand, cand + K);
@@ -132,65 +108,30 @@ int nemo_lineage_cuts(nemo_ctx *c, uint32_t iteration, int cond, const uint32_t 
   } else {
     cs.lin_cand.clear();
   }
-  nemo::LinArgs a{};
-  a.graph = g, a.cand = cs.d_lncand.p;
-  a.lds_total = lds_total, a.region = cs.d_lnreg.p, a.region_words = rw;
-  const double img = wit::image_bytes((double)V, (double)E, (double)L);
-  auto level_limit = [&](uint64_t n_front, uint32_t d) -> int {
-    if (lin::front_fits(n_front)) return NEMO_OK;
-    return fail(c, NEMO_ERR_LIMIT, "nemo_lineage_cuts: a frontier of %llu sets of size %u exceeds 2^32 - 2: shorten the candidate list",
-                (unsigned long long)n_front, d);
+  LinSearch ls{who, g, max_size, wit::lds_fits, wit::wit_lds_bytes, wit::glob_words, wit::image_bytes, nemo::lin_lds_resident, "k_lin_lds",
+               "k_lin_glob"};
+  ls.glob_node_bytes = 32.0, ls.stats = cs.lin_stats;  // the dead and the need words
+  auto launch = [&](const nemo::LinArgs &a, bool lds, uint32_t grid) {
+    if (lds) nemo::launch_lin_lds(cs.dc, a, grid, s);
+    else nemo::launch_lin_glob(cs.dc, a, grid, s);
   };
-  auto prepare = [](uint32_t, uint64_t, uint64_t) { return NEMO_OK; };  // nothing is sized by the level
-  auto evaluate = [&](int, double *by, double *op) -> int {
-    const uint64_t ck = a.n_chunks;
-    const uint32_t grid = lin::grid(ck, resident, cap);
-    // the byte model: a workgroup reads the image once (wit_host.h); a set is 16 bytes read; the global tier adds
-    // 32 V per chunk for its two word arrays; the children are not known at the launch and are left out; ops = 2 E
-    // child words per chunk, one sweep up and one pass down
-    const double b = grid * img + 16.0 * (double)a.n_front + (lds ? 0.0 : (double)ck * 32.0 * (double)V), o = (double)ck * 2.0 * (double)E;
-    *by += b, *op += o;
-    if (lds) return timed(c, "k_lin_lds", b, o, [&] { nemo::launch_lin_lds(cs.dc, a, grid, s); });
-    return timed(c, "k_lin_glob", b, o, [&] { nemo::launch_lin_glob(cs.dc, a, grid, s); });
-  };
-  auto emit_bound = [&](uint64_t n_front, uint32_t d) { return lin::emit_bound(n_front, K, d); };
-  uint64_t n_cuts = 0;
-  if ((rc = lin_levels(c, who, "candidate list", cs.d_ln, c->h_lin, c->ev_lin, a, K, max_size, cs.lin_stats, nullptr, level_limit, prepare, evaluate,
-                       emit_bound, &bytes, &ops, &n_cuts)))
+  if ((rc = lin_node_search(c, ls, cs.d_ln, cs.d_lnreg, cs.d_lncand, cs.lin_cand, c->h_lin, c->ev_lin, L, timer, bytes, &cs.lin_rows, launch,
+                            lin_search_goes_on)))
     return rc;
-  timer.done(bytes, ops);
-  // the rows, sorted by (size, colex)
-  LinCuts cuts;
-  if ((rc = lin_sorted_keys(c, cs.d_ln, nullptr, c->h_lin, c->ev_lin, n_cuts, &cuts))) return rc;
-  cs.lin_rows.resize(n_cuts);
-  for (uint64_t i = 0; i < n_cuts; i++) {
-    nemo_lineage_cut &row = cs.lin_rows[i];
-    uint32_t pos[LIN_MAX_SIZE];
-    row.size = lin::key_unpack(cuts.keys[cuts.order[i]], pos);
-    for (uint32_t j = 0; j < LIN_MAX_SIZE; j++) row.node[j] = j < row.size ? cs.lin_cand[pos[j]] : 0xFFFFFFFFu;
-  }
   cs.lin_done = true;
   return NEMO_OK;
 }
 
 int nemo_fetch_lineage_cuts(nemo_ctx *c, nemo_lineage_cut *out, uint64_t cap, uint64_t *n_out) {
   if (!c) return NEMO_ERR_INVALID;
-  if (c->node || !c->cs.lin_done)
-    return fail(c, NEMO_ERR_STATE, "nemo_fetch_lineage_cuts before nemo_lineage_cuts (or after a later nemo_load_corpus)");
-  const uint64_t n = c->cs.lin_rows.size();  // no ensure_whole: reads the last call's host rows, no graph
-  if (n_out) *n_out = n;
-  if (!out) return NEMO_OK;
-  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
-  if (n) memcpy(out, c->cs.lin_rows.data(), n * sizeof(nemo_lineage_cut));
-  return NEMO_OK;
+  const std::vector<nemo_lineage_cut> &rows = c->cs.lin_rows;
+  return fetch_result(c, c->cs.lin_done, "nemo_fetch_lineage_cuts", "nemo_lineage_cuts", rows.data(), rows.size(), sizeof(nemo_lineage_cut), out, cap,
+                      n_out);
 }
 
 int nemo_fetch_lineage_cut_stats(nemo_ctx *c, uint64_t out[18]) {
   if (!c || !out) return NEMO_ERR_INVALID;
-  if (c->node || !c->cs.lin_done)
-    return fail(c, NEMO_ERR_STATE, "nemo_fetch_lineage_cut_stats before nemo_lineage_cuts (or after a later nemo_load_corpus)");
-  memcpy(out, c->cs.lin_stats, sizeof c->cs.lin_stats);
-  return NEMO_OK;
+  return fetch_result(c, c->cs.lin_done, "nemo_fetch_lineage_cut_stats", "nemo_lineage_cuts", c->cs.lin_stats, 18, 8, out, 18, nullptr);
 }
 
 }  // extern "C"

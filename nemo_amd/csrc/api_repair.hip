@@ -1,8 +1,10 @@
 // api_repair.hip — nemo_min_repair_sets, nemo_min_repairs and their fetches (k_repair.hip, repair_host.h; DESIGN.md
-// §Minimal repair sets).  The calls keep their entry checks and their absent set and candidate source; the search from
+// §Minimal repair sets).  The calls keep their entry checks and early ends; the absent set and the candidates reach
+// the device through repair_api.h's front end, shared with api_lrepair.hip, on the calls' own state; the search from
 // there to the rows is cut_api.h's node_search, shared with api_cuts.hip, with a round 0, the bitmap in the image
 // and the status decided from round 0's word.
 #include "cut_api.h"
+#include "repair_api.h"
 
 namespace {
 
@@ -16,7 +18,7 @@ int repair_end(nemo_ctx *c, uint32_t status, uint64_t n_absent) {
   return NEMO_OK;
 }
 
-// The search over graph g with the bitmap in d_rpbits and the K candidates in rp.cand (both queued on the stream), L
+// The search over graph g with the bitmap in rp_abs.d_bits and the K candidates in rp.cand (both queued on the stream), L
 // Kahn levels and n_absent absent nodes.  from_dev: rp.h_cand is not known yet (the pair form).  Round 0's word
 // decides the status; a status other than SEARCHED ends the call (round 1 was wasted).
 int repair_search(nemo_ctx *c, const char *who, uint32_t g, uint32_t max_size, uint64_t K, uint32_t L, uint64_t n_absent, bool from_dev,
@@ -25,7 +27,7 @@ int repair_search(nemo_ctx *c, const char *who, uint32_t g, uint32_t max_size, u
   hipStream_t s = c->stream;
   NodeSearch ns{who, g, max_size, repair::lds_fits, repair::repair_lds_bytes, nemo::repair_lds_resident, "k_repair_lds", "k_repair_glob"};
   auto launch = [&](const nemo::CutArgs &a, bool lds, uint32_t grid, uint32_t lds_bytes) {
-    const nemo::RepairArgs ra{a, cs.d_rpbits.p, (uint32_t)K};
+    const nemo::RepairArgs ra{a, cs.rp_abs.d_bits.p, (uint32_t)K};
     if (lds) nemo::launch_repair_lds(cs.dc, ra, grid, lds_bytes, s);
     else nemo::launch_repair_glob(cs.dc, ra, grid, s);
   };
@@ -64,39 +66,15 @@ int nemo_min_repair_sets(nemo_ctx *c, uint32_t iteration, int cond, const uint32
   if ((rc = run_index(c, iteration, &r))) return rc;
   const uint32_t g = 2 * r + (uint32_t)cond;
   const uint64_t V = cs.nv(g);
-  {
-    size_t where = 0;
-    switch (repair::check_lists(absent, n_absent, cand, n_cand, V, &where)) {
-      case repair::ABSENT_RANGE:
-        return fail(c, NEMO_ERR_INVALID, "%s: absent node %zu is node %u, out of range (%llu nodes)", who, where, absent[where],
-                    (unsigned long long)V);
-      case repair::ABSENT_DUP:
-        return fail(c, NEMO_ERR_INVALID, "%s: absent node %zu names node %u a second time", who, where, absent[where]);
-      case repair::CAND_DUP:
-        return fail(c, NEMO_ERR_INVALID, "%s: candidate %zu names node %u a second time", who, where, cand[where]);
-      case repair::CAND_NOT_ABSENT:
-        return fail(c, NEMO_ERR_INVALID, "%s: candidate %zu is node %u, which is not in the absent list", who, where, cand[where]);
-      default:
-        break;
-    }
-  }
+  if ((rc = absent_check(c, who, absent, n_absent, cand, n_cand, V))) return rc;
   const uint64_t K = cand ? n_cand : n_absent;
   cs.rp.h_cand.assign(cand ? cand : absent, (cand ? cand : absent) + K);
   if (n_absent == 0) return repair_end(c, REPAIR_HOLDS, 0);  // nothing is lost
   if ((rc = ensure_event(c, &c->ev_repair))) return rc;
   if ((rc = c->h_repair.grow(c, 8))) return rc;
-  hipStream_t s = c->stream;
   GroupTimer timer(c, "k_repair");
-  {
-    const uint64_t need[2] = {repair::bitmap_words(V), std::max<uint64_t>(K, 1)};
-    if ((rc = grow_group(c, need, cs.d_rpbits, cs.rp.cand))) return rc;
-  }
-  cs.rp_bits = repair::bitmap(absent, n_absent, V);
-  HIPCHK(c, hipMemcpyAsync(cs.d_rpbits.p, cs.rp_bits.data(), 8 * cs.rp_bits.size(), hipMemcpyHostToDevice, s));
-  if (K) HIPCHK(c, hipMemcpyAsync(cs.rp.cand.p, cs.rp.h_cand.data(), 4 * K, hipMemcpyHostToDevice, s));
-  nemo::launch_to_host(c->h_repair.p, cs.dc.nlev + g, 4, s);  // the graph's Kahn level count, for the tier
-  if ((rc = wait_copied(c, c->ev_repair))) return rc;
-  const uint32_t L = c->h_repair.p[0];
+  uint32_t L;
+  if ((rc = absent_queue(c, cs.rp_abs, cs.rp.cand, cs.rp.h_cand, c->h_repair, c->ev_repair, g, absent, n_absent, &L))) return rc;
   return repair_search(c, who, g, max_size, K, L, n_absent, false, timer, 0.0);
 }
 
@@ -117,45 +95,13 @@ int nemo_min_repairs(nemo_ctx *c, uint32_t base_iter, uint32_t other_iter, uint3
   const uint64_t V = cs.nv(g);
   cs.rp.h_cand.clear();
   if (V == 0) return repair_end(c, REPAIR_HOLDS, 0);
-  const pairs::Plan plan = pairs::plan(&go, 1, cs.node_off.data(), cs.run0 >= 0 ? (int64_t)cs.g0() : -1);
-  if (!plan.ok) return fail(c, NEMO_ERR_LIMIT, "%s: a label table would exceed 2^32 slots", who);
-  const bool shared = plan.entry_tab[0] == PAIRS_SHARED;
   if ((rc = ensure_event(c, &c->ev_repair))) return rc;
   if ((rc = c->h_repair.grow(c, 8))) return rc;
-  hipStream_t s = c->stream;
   GroupTimer timer(c, "k_repair");
-  if (!cs.d_rpcnt.p || (!shared && (!cs.d_rptab.p || plan.words > cs.d_rphreg.cap || !cs.d_rphreg.p))) {
-    HIPCHK(c, hipStreamSynchronize(s));  // an earlier call may still use them
-    if ((rc = cs.d_rpcnt.grow(c, 2))) return rc;
-    if (!shared && ((rc = cs.d_rptab.grow(c, 1)) || (rc = cs.d_rphreg.grow(c, plan.words)))) return rc;
-  }
-  {
-    const uint64_t need[2] = {repair::bitmap_words(V), V};
-    if ((rc = grow_group(c, need, cs.d_rpbits, cs.rp.cand))) return rc;
-  }
   double bytes = 0;
-  cs.rp_tab = shared ? nemo::LabTab{cs.d_r0hkey, cs.r0hmask, go} : nemo::LabTab{cs.d_rphreg.p, plan.tab_mask[0], go};
-  if (!shared) {
-    HIPCHK(c, hipMemcpyAsync(cs.d_rptab.p, &cs.rp_tab, sizeof(nemo::LabTab), hipMemcpyHostToDevice, s));
-    const uint32_t lds_max = c->opt.pair_hash_lds_max;
-    const uint32_t lds_slots = plan.tab_mask[0] < lds_max ? plan.tab_mask[0] + 1u : 0u;
-    const double b = 8.0 * (double)plan.nodes + 4.0 * (double)plan.words;
-    if ((rc = timed(c, "k_lab_hash", b, 0, [&] { nemo::launch_lab_hash(cs.dc, cs.d_rptab.p, 1, lds_max, lds_slots, s); }))) return rc;
-    bytes += b;
-  }
-  {
-    // node word, label and two row pointers of every node, a probe per sink goal, the bitmap and the list written
-    const double b = 20.0 * (double)V + (double)V / 8.0 + 8.0;
-    if ((rc = timed(c, "k_repair_absent", b, 0, [&] {
-           nemo::launch_repair_absent(cs.dc, g, cs.rp_tab.key, cs.rp_tab.mask, cs.d_rpbits.p, cs.rp.cand.p, cs.d_rpcnt.p, s);
-         })))
-      return rc;
-    bytes += b;
-  }
-  nemo::launch_to_host(c->h_repair.p, cs.d_rpcnt.p, 8, s);  // the count beside the Kahn level count
-  if ((rc = wait_copied(c, c->ev_repair))) return rc;
-  const uint64_t K = c->h_repair.p[0];
-  const uint32_t L = c->h_repair.p[1];
+  uint64_t K;
+  uint32_t L;
+  if ((rc = absent_pair(c, who, cs.rp_abs, cs.rp.cand, c->h_repair, c->ev_repair, g, go, &bytes, &K, &L))) return rc;
   if (K == 0) {  // every sink goal's label is a goal label of the other run
     timer.done(bytes, 0);
     return repair_end(c, REPAIR_HOLDS, 0);
@@ -167,18 +113,18 @@ static const char *const REPAIR_CALLS = "nemo_min_repair_sets / nemo_min_repairs
 
 int nemo_fetch_min_repairs(nemo_ctx *c, nemo_repair *out, uint64_t cap, uint64_t *n_out) {
   if (!c) return NEMO_ERR_INVALID;
-  return node_search_fetch(c, c->cs.rp, "nemo_fetch_min_repairs", REPAIR_CALLS, c->h_repair.p, c->cs.rp.n_rows, sizeof(nemo_repair), out, cap, n_out);
+  return fetch_result(c, c->cs.rp.done, "nemo_fetch_min_repairs", REPAIR_CALLS, c->h_repair.p, c->cs.rp.n_rows, sizeof(nemo_repair), out, cap, n_out);
 }
 
 int nemo_fetch_min_repair_stats(nemo_ctx *c, uint64_t out[11]) {
   if (!c || !out) return NEMO_ERR_INVALID;
-  return node_search_fetch(c, c->cs.rp, "nemo_fetch_min_repair_stats", REPAIR_CALLS, c->cs.rp_stats, 11, 8, out, 11, nullptr);
+  return fetch_result(c, c->cs.rp.done, "nemo_fetch_min_repair_stats", REPAIR_CALLS, c->cs.rp_stats, 11, 8, out, 11, nullptr);
 }
 
 int nemo_fetch_min_repair_cands(nemo_ctx *c, uint32_t *out, uint64_t cap, uint64_t *n_out) {
   if (!c) return NEMO_ERR_INVALID;
   const std::vector<uint32_t> &cand = c->cs.rp.h_cand;
-  return node_search_fetch(c, c->cs.rp, "nemo_fetch_min_repair_cands", REPAIR_CALLS, cand.data(), cand.size(), 4, out, cap, n_out);
+  return fetch_result(c, c->cs.rp.done, "nemo_fetch_min_repair_cands", REPAIR_CALLS, cand.data(), cand.size(), 4, out, cap, n_out);
 }
 
 }  // extern "C"

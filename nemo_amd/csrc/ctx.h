@@ -145,6 +145,20 @@ struct CutBufs {
   bool done = false;
 };
 
+// The absent set of one family of repair calls (repair_api.h's front ends): the exhaustive calls keep one, the lineage
+// calls another.  Each buffer grows only inside its family's calls, to the largest request so far, behind a wait for
+// the stream: d_cnt, d_tab and d_hreg before anything is counted (the pair form alone; the last two with other !=
+// run 0); d_bits and the family's candidate buffer together once the graph is known (the pair form's list has room
+// for every node).
+struct AbsentSet {
+  std::vector<uint64_t> bits;      // the last call's bitmap (the explicit form)
+  nemo::LabTab tab{};              // ... and the pair form's table
+  DevBuf<uint32_t> d_cnt;          // [2] the pair form's (absent sinks, Kahn levels)
+  DevBuf<nemo::LabTab> d_tab;      // [1] the table k_lab_hash fills (the pair form, other != run 0)
+  DevBuf<uint32_t> d_hreg;         // ... and its slots
+  DevBuf<uint64_t> d_bits;         // [repair::bitmap_words(V)] the absent bitmap
+};
+
 // Graph g = nodes [node_off[g], node_off[g + 1]), edges likewise; run r's graphs are 2r (pre) and 2r + 1 (post).
 struct GraphSizes {
   std::vector<uint64_t> node_off, edge_off;
@@ -372,17 +386,10 @@ struct CorpusState : GraphSizes {
 
   // minimal repair sets (k_repair.hip): the two calls' own state, void after the next of them or a load; independent
   // of every other call's state.  Each buffer grows only inside the two calls, to the largest request so far, behind a
-  // wait for the stream: d_rpcnt, d_rptab and d_rphreg before anything is counted (the last two: the pair form alone);
-  // d_rpbits and rp.cand together once the graph is known (the pair form's list has room for every node); the rest as
-  // CutBufs states
+  // wait for the stream: rp_abs as AbsentSet states, its bitmap together with rp.cand; the rest as CutBufs states
   CutBufs rp;                        // the search's (rows in nemo_ctx::h_repair); w[0]: round 0's word behind round 1's
   uint64_t rp_stats[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // status, |A|, then per size: live candidates, hypotheses, minimal repairs
-  std::vector<uint64_t> rp_bits;     // the last call's bitmap (the explicit form)
-  nemo::LabTab rp_tab{};             // ... and the pair form's table
-  DevBuf<uint32_t> d_rpcnt;          // [2] the pair form's (absent sinks, Kahn levels)
-  DevBuf<nemo::LabTab> d_rptab;      // [1] the table k_lab_hash fills (the pair form, other != run 0)
-  DevBuf<uint32_t> d_rphreg;         // ... and its slots
-  DevBuf<uint64_t> d_rpbits;         // [repair::bitmap_words(V)] the absent bitmap
+  AbsentSet rp_abs;                  // the absent set (repair_api.h)
 
   // knock-out by label (k_klabel.hip): the call's own state, void after the next nemo_knockout_labels or load;
   // independent of knock-out, cut, diff, nearest and class state.  The eight buffers grow as one group, only
@@ -476,8 +483,8 @@ struct CorpusState : GraphSizes {
   // lineage-driven cut search (k_lineage.hip): the call's own state, void after the next nemo_lineage_cuts or load;
   // independent of every other call's state (kl_nlev above is the load's, not a result).  One group d_ln*, which grows
   // only inside nemo_lineage_cuts, each buffer to the largest request so far, behind a wait for the stream: d_lndesc
-  // alone, before anything is counted; d_lncand, d_ln.ctr and d_lnreg together once the candidates are known, in this
-  // order; the rest of d_ln as LinBufs states
+  // alone, before anything is counted; d_lncand alone once the candidates are counted; d_ln.ctr and d_lnreg together
+  // once the tier is known (lin_api.h's lin_node_search), in this order; the rest of d_ln as LinBufs states
   bool lin_done = false;
   uint64_t lin_stats[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // per size 0..8: sets evaluated, minimal cuts
   std::vector<nemo_lineage_cut> lin_rows;  // the last call's rows, sorted
@@ -512,20 +519,14 @@ struct CorpusState : GraphSizes {
 
   // lineage repair search (k_lrepair.hip): the two calls' own state, void after the next nemo_lineage_repair_sets /
   // nemo_lineage_repairs or load; independent of every other call's state (kl_nlev above is the load's, not a result).
-  // One group d_lr*, which grows only inside the two calls, each buffer to the largest request so far, behind a wait
-  // for the stream: d_lrcnt, d_lrtab and d_lrhreg before anything is counted (the pair form alone); d_lrbits and
-  // d_lrcand together once the graph is known (the pair form's list has room for every node); d_lr.ctr and d_lrreg
-  // together once the candidates are counted; the rest of d_lr as LinBufs states
+  // One group, which grows only inside the two calls, each buffer to the largest request so far, behind a wait for the
+  // stream: lr_abs as AbsentSet states, its bitmap together with d_lrcand; d_lr.ctr and d_lrreg together once the tier
+  // is known (lin_api.h's lin_node_search), in this order; the rest of d_lr as LinBufs states
   bool lr_done = false;
   uint64_t lr_stats[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // status, |A|, then per size 0..8: sets evaluated, minimal repairs
   std::vector<nemo_lineage_repair> lr_rows;  // the last call's rows, sorted
   std::vector<uint32_t> lr_cand;     // the last call's candidates (nodes)
-  std::vector<uint64_t> lr_bits;     // the last call's bitmap (the explicit form)
-  nemo::LabTab lr_tab{};             // ... and the pair form's table
-  DevBuf<uint32_t> d_lrcnt;          // [2] the pair form's (absent sinks, Kahn levels)
-  DevBuf<nemo::LabTab> d_lrtab;      // [1] the table k_lab_hash fills (the pair form, other != run 0)
-  DevBuf<uint32_t> d_lrhreg;         // ... and its slots
-  DevBuf<uint64_t> d_lrbits;         // [repair::bitmap_words(V)] the absent bitmap
+  AbsentSet lr_abs;                  // the absent set (repair_api.h)
   DevBuf<uint32_t> d_lrcand;         // [K] candidate position -> node
   DevBuf<uint64_t> d_lrreg;          // k_lrep_glob: dead, blame and stop-rule words of every workgroup of the launch
   LinBufs d_lr;                      // the level loop's; ctr[3]: the two-hypothesis launch's lost word

@@ -1,10 +1,11 @@
 // cut_api.h — the host code the two searches of sets of size <= 3 over one graph share (api_cuts.hip: nemo_min_cuts;
 // api_repair.hip: nemo_min_repair_sets, nemo_min_repairs; DESIGN.md §Minimal cut sets, §Minimal repair sets): the
-// entry checks, the search from "the candidates are on the device" to the rows, and the fetches' copy.  What a round
-// launches, its tier rule and what round 1's words decide are the calling entry point's, passed in NodeSearch and two callables.  The
-// storage is the calling entry point's (ctx.h: its CutBufs, pinned buffer and event, handed in); while a search runs
-// the driver owns it: it grows every buffer of the CutBufs but cand, grows the pinned buffer and waits on the event.
-// The rounds' sizes and the rows are knock_api.h's; the arithmetic is cut_host.h's.
+// entry checks and the search from "the candidates are on the device" to the rows (the fetches' copy is knock_api.h's
+// fetch_result).  What a round launches, its tier rule and what round 1's words decide are the calling entry point's,
+// passed in NodeSearch and two callables.  The storage is the calling entry point's (ctx.h: its CutBufs, pinned buffer
+// and event, handed in); while a search runs the driver owns it: it grows every buffer of the CutBufs but cand, grows
+// the pinned buffer and waits on the event.  The rounds' sizes and the rows are knock_api.h's; the arithmetic is
+// cut_host.h's.
 #pragma once
 #include "knock_api.h"
 
@@ -149,16 +150,4 @@ static int node_search(nemo_ctx *c, const NodeSearch &ns, CutBufs &b, Pinned<uin
   }
   const CutOut out = {h, ev, b.scan, b.rows, 4, ns.stats, &b.n_rows, &b.done};
   return cut_rows(c, out, rd, a, max_size, timer, bytes, ops);
-}
-
-// A fetch of the last call's host data (no ensure_whole: no graph is read): n elements of `elem` bytes at src into
-// out[cap].  who: the fetch; calls: the calls that make its result.
-static inline int node_search_fetch(nemo_ctx *c, const CutBufs &b, const char *who, const char *calls, const void *src, uint64_t n, size_t elem,
-                                    void *out, uint64_t cap, uint64_t *n_out) {
-  if (c->node || !b.done) return fail(c, NEMO_ERR_STATE, "%s before %s (or after a later nemo_load_corpus)", who, calls);
-  if (n_out) *n_out = n;
-  if (!out) return NEMO_OK;
-  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
-  if (n) memcpy(out, src, n * elem);
-  return NEMO_OK;
 }

@@ -1,5 +1,6 @@
 // knock_api.h — the host code the knock-out family's calls share (api_knock.hip, api_cuts.hip, api_klabel.hip,
-// api_lcuts.hip, api_gcuts.hip, api_witness.hip): the wait for a call's copies to pinned memory, the dynamic LDS of a persistent
+// api_lcuts.hip, api_gcuts.hip, api_witness.hip): the wait for a call's copies to pinned memory, the fetches' copy of a
+// call's host data (the cut, repair and lineage searches' fetches), the dynamic LDS of a persistent
 // LDS-tier launch, the listed graphs' split into the two tiers (api_klabel.hip, api_lcuts.hip, api_gcuts.hip), and the
 // rounds' sizes and the rows of the cut and repair searches (cut_api.h for api_cuts.hip and api_repair.hip;
 // api_lcuts.hip, api_gcuts.hip), and the rounds' limits, launch plans and driver of the two searches by label
@@ -15,6 +16,18 @@
 static inline int wait_copied(nemo_ctx *c, hipEvent_t ev) {
   HIPCHK(c, hipEventRecord(ev, c->stream));
   HIPCHK(c, hipEventSynchronize(ev));
+  return NEMO_OK;
+}
+
+// A fetch of the last call's host data (no ensure_whole: no graph is read): n elements of `elem` bytes at src into
+// out[cap].  done: the call's result stands; who: the fetch; calls: the calls that make its result.
+static inline int fetch_result(nemo_ctx *c, bool done, const char *who, const char *calls, const void *src, uint64_t n, size_t elem, void *out,
+                               uint64_t cap, uint64_t *n_out) {
+  if (c->node || !done) return fail(c, NEMO_ERR_STATE, "%s before %s (or after a later nemo_load_corpus)", who, calls);
+  if (n_out) *n_out = n;
+  if (!out) return NEMO_OK;
+  if (cap < n) return fail(c, NEMO_ERR_INVALID, "capacity too small");
+  if (n) memcpy(out, src, n * elem);
   return NEMO_OK;
 }
 

@@ -1,8 +1,10 @@
-// lin_api.h — the host code the two lineage searches share (api_lineage.hip: nemo_lineage_cuts; api_lgcuts.hip:
-// nemo_lineage_group_cuts; DESIGN.md §Lineage-driven cut search): the level loop of the hitting-set tree, with the
-// rule by which a level runs again behind a grown emission buffer (lin_host.h's lin::level_end), and the cuts' way to
-// the host.  What a level evaluates, its limits and its bound are the calling entry point's, passed as callables.
-// Every call keeps its own event, pinned buffer, LinBufs and state (ctx.h); nothing here owns any.
+// lin_api.h — the host code the lineage searches share (api_lineage.hip: nemo_lineage_cuts; api_lgcuts.hip:
+// nemo_lineage_group_cuts; api_lrepair.hip: nemo_lineage_repair_sets, nemo_lineage_repairs; DESIGN.md §Lineage-driven
+// cut search): the level loop of the hitting-set tree, with the rule by which a level runs again behind a grown
+// emission buffer (lin_host.h's lin::level_end), and the found sets' way to the host; and, for the searches over one
+// graph (the cuts and the repairs), the tail from the tier choice to the rows, lin_node_search.  What a level
+// evaluates, its limits and its bound are the calling entry point's, passed as callables.  Every call keeps its own
+// event, pinned buffer, LinBufs and state (ctx.h); nothing here owns any.
 #pragma once
 #include "knock_api.h"
 
@@ -131,5 +133,98 @@ static inline int lin_sorted_keys(nemo_ctx *c, const LinBufs &b, const DevBuf<ui
     if (col) out->col[i] = hn[i];
   }
   std::sort(out->order.begin(), out->order.end(), [&](uint32_t x, uint32_t y) { return lin::row_less(out->keys[x], out->keys[y]); });
+  return NEMO_OK;
+}
+
+struct LinSearch {  // what differs between the two lineage searches over one graph, beside their launch and before callables
+  const char *who;
+  uint32_t g;         // 2r + cond
+  uint32_t max_size;
+  bool (*lds_fits)(uint64_t V, uint64_t E, uint64_t L, uint32_t lds_max);  // the tier rule (option wit_lds_max)
+  uint32_t (*lds_bytes)(uint32_t V, uint32_t E, uint32_t L);               // ... and the LDS tier's image
+  uint64_t (*glob_words)(uint64_t V);                      // a workgroup's region on the global tier, in u64
+  double (*image_bytes)(double V, double E, double L);     // the bytes a workgroup reads to stage the graph
+  uint32_t (*lds_resident)(uint32_t lds_bytes, uint32_t n_cu);  // the resident workgroups of the LDS-tier kernel
+  const char *lds_name, *glob_name;  // the evaluations' timing names
+  double glob_node_bytes;  // the global tier's bytes per node per chunk: 16 per word array of the region
+  uint64_t *stats;         // [18] per size 0..8: sets evaluated, sets found
+};
+
+// a search with nothing to do before the levels (nemo_lineage_cuts)
+static inline bool lin_search_goes_on(const nemo::LinArgs &, bool, double *, double *, int *) { return false; }
+
+// The rows of both searches are {size, node[8]}: one layout, filled by one loop.
+static_assert(sizeof(nemo_lineage_cut) == sizeof(nemo_lineage_repair) && offsetof(nemo_lineage_cut, node) == offsetof(nemo_lineage_repair, node),
+              "nemo_lineage_cut and nemo_lineage_repair share one layout");
+
+// The search over graph ls.g with its candidates h_cand in d_cand (queued on the stream) and L Kahn levels, from the
+// tier choice to the rows: the tier and the launch's LDS, the grid (as many workgroups as are resident, at most one
+// per chunk), the growth of b.ctr and the workgroups' region together, the level loop, and the found sets as rows
+// sorted by (size, colex), their positions turned into nodes through h_cand.  h / ev: the call's pinned buffer (8
+// elements at least) and event; bytes: what the call has moved so far.  The call's own, as node_search takes its
+// callables:
+//   launch(a, lds, grid)                  the evaluation of level `a` on the tier
+//   before(a, lds, &bytes, &ops, &rc)     once the buffers are grown and `a` names them, before the levels (the
+//                                         repairs' two-hypothesis launch): true ends the call with rc, and the timing
+//                                         group is the hook's to end
+// The byte model of a level: a workgroup reads the image once; a set is 16 bytes read; the global tier adds
+// ls.glob_node_bytes V per chunk for its word arrays; the children are not known at the launch and are left out;
+// ops = 2 E child words per chunk, one sweep up and one pass down.  Ends the call's timing group behind the levels.
+template <class Row, class LA, class BE>
+static int lin_node_search(nemo_ctx *c, const LinSearch &ls, LinBufs &b, DevBuf<uint64_t> &region, const DevBuf<uint32_t> &d_cand,
+                           const std::vector<uint32_t> &h_cand, Pinned<uint64_t> &h, hipEvent_t ev, uint32_t L, GroupTimer &timer, double bytes,
+                           std::vector<Row> *rows, LA &&launch, BE &&before) {
+  CorpusState &cs = c->cs;
+  const char *who = ls.who;
+  const uint64_t V = cs.nv(ls.g), E = cs.ne(ls.g), K = h_cand.size();
+  int rc;
+  double ops = 0;
+  const bool lds = ls.lds_fits(V, E, L, c->opt.wit_lds_max);
+  const uint32_t image = lds ? ls.lds_bytes((uint32_t)V, (uint32_t)E, L) : 0u;
+  const uint64_t rw = lds ? 0 : ls.glob_words(V);
+  uint32_t lds_total = 0, res_lds = 1;
+  if (lds && (rc = ko_lds_total(c, who, ls.lds_name, [&](uint32_t by) { return ls.lds_resident(by, cs.dc.n_cu); }, image, 0, 4096, &lds_total,
+                                &res_lds)))
+    return rc;
+  const uint32_t cap = c->opt.kl_grid;
+  const uint64_t resident = lds ? res_lds : klabel::region_grid(2ull * cs.dc.n_cu, rw);
+  {
+    const uint64_t need[2] = {4, std::max<uint64_t>(1, rw * lin::grid(~0ull, resident, cap))};
+    if ((rc = grow_group(c, need, b.ctr, region))) return rc;
+  }
+  nemo::LinArgs a{};
+  a.graph = ls.g, a.cand = d_cand.p, a.K = (uint32_t)K, a.ctr = b.ctr.p;
+  a.lds_total = lds_total, a.region = region.p, a.region_words = rw;
+  if (before(a, lds, &bytes, &ops, &rc)) return rc;
+  const double img = ls.image_bytes((double)V, (double)E, (double)L);
+  auto level_limit = [&](uint64_t n_front, uint32_t d) -> int {
+    if (lin::front_fits(n_front)) return NEMO_OK;
+    return fail(c, NEMO_ERR_LIMIT, "%s: a frontier of %llu sets of size %u exceeds 2^32 - 2: shorten the candidate list", who,
+                (unsigned long long)n_front, d);
+  };
+  auto prepare = [](uint32_t, uint64_t, uint64_t) { return NEMO_OK; };  // nothing is sized by the level
+  auto evaluate = [&](int, double *by, double *op) -> int {
+    const uint64_t ck = a.n_chunks;
+    const uint32_t grid = lin::grid(ck, resident, cap);
+    const double bt = grid * img + 16.0 * (double)a.n_front + (lds ? 0.0 : (double)ck * ls.glob_node_bytes * (double)V);
+    const double o = (double)ck * 2.0 * (double)E;
+    *by += bt, *op += o;
+    return timed(c, lds ? ls.lds_name : ls.glob_name, bt, o, [&] { launch(a, lds, grid); });
+  };
+  auto emit_bound = [&](uint64_t n_front, uint32_t d) { return lin::emit_bound(n_front, K, d); };
+  uint64_t n_found = 0;
+  if ((rc = lin_levels(c, who, "candidate list", b, h, ev, a, K, ls.max_size, ls.stats, nullptr, level_limit, prepare, evaluate, emit_bound,
+                       &bytes, &ops, &n_found)))
+    return rc;
+  timer.done(bytes, ops);
+  LinCuts found;
+  if ((rc = lin_sorted_keys(c, b, nullptr, h, ev, n_found, &found))) return rc;
+  rows->resize(n_found);
+  for (uint64_t i = 0; i < n_found; i++) {
+    Row &row = (*rows)[i];
+    uint32_t pos[LIN_MAX_SIZE];
+    row.size = lin::key_unpack(found.keys[found.order[i]], pos);
+    for (uint32_t j = 0; j < LIN_MAX_SIZE; j++) row.node[j] = j < row.size ? h_cand[pos[j]] : 0xFFFFFFFFu;
+  }
   return NEMO_OK;
 }

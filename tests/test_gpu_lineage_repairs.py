@@ -617,17 +617,31 @@ def test_other_results_are_left_alone(eng):
     reps = eng.min_repair_sets(0, 1, sinks, None, 3).copy()
     rep_stats = eng.min_repair_stats()
     assert len(cuts) == 4 and len(reps) == 0
+
+    def exhaustive_unchanged(rows, stats, what):  # rows, status, |A|, the round stats and the candidate list
+        st = eng.min_repair_stats()
+        assert np.array_equal(eng.min_repair_rows(), rows) and st[:2] == stats[:2] and np.array_equal(st[2], stats[2]), what
+        assert np.array_equal(st[3], stats[3]), f"{what}: the candidate list differs"
+
     want = check(eng, corpus, 0, sinks, None, 4, "between the other calls", gr)
     eng.lineage_repairs(1, 0, 2)
     check(eng, corpus, 1, [3, 4, 5], [3, 5], 8, "another graph")
     assert np.array_equal(eng.lineage_cut_rows(), cuts) and np.array_equal(eng.lineage_cut_stats(), cut_stats)
-    st = eng.min_repair_stats()
-    assert np.array_equal(eng.min_repair_rows(), reps) and st[:2] == rep_stats[:2] and np.array_equal(st[2], rep_stats[2])
-    assert np.array_equal(st[3], rep_stats[3])
-    # and the reverse
+    exhaustive_unchanged(reps, rep_stats, "after the lineage repair calls")
+    # and the reverse (compare reads the lineage calls' candidate list too)
     check(eng, corpus, 0, sinks, None, 4, "before the other calls", gr, want=want)
     eng.lineage_cuts(1, 1, None, 3)
     eng.min_repair_sets(1, 1, [3, 4], None, 2)
     eng.min_repairs(0, 1, 2)
     eng.min_cuts(0, 1, None, 2)
     compare(eng, eng.lineage_repair_rows(), want, "after the other calls")
+    # the two pair forms against run 1, which is not run 0: each family fills a label table of its own.  Every label
+    # of the corpus is distinct, so the absent set is every sink goal of the product graph, in node order
+    compare(eng, eng.lineage_repairs(0, 1, 4), want, "the pair form")
+    pair = eng.min_repairs(0, 1, 3).copy()
+    pair_stats = eng.min_repair_stats()
+    assert pair_stats[0] == SEARCHED and pair_stats[1] == len(sinks) and pair_stats[3].tolist() == sinks and len(pair) == 0
+    compare(eng, eng.lineage_repair_rows(), want, "the pair form, after the exhaustive pair form")
+    eng.lineage_repairs(0, 1, 2)  # the lineage family's table once more, another result
+    assert len(eng.lineage_repair_rows()) == 0 and eng.lineage_repair_cands().tolist() == sinks
+    exhaustive_unchanged(pair, pair_stats, "the exhaustive pair form, after the lineage pair form")

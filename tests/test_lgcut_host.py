@@ -122,18 +122,26 @@ def test_host_header_reuses_and_kernels_share():
     assert claims == ["lin_dev.h"] and dev.count("atomicAdd(l.ctr + 1,") == 1
     api = open(os.path.join(CSRC, "api_lgcuts.hip")).read()
     api_lin = open(os.path.join(CSRC, "api_lineage.hip")).read()
+    api_lrep = open(os.path.join(CSRC, "api_lrepair.hip")).read()
     for name in ('GroupTimer timer(c, "k_lgcuts")', "launch_gc_table(", "launch_gc_rows(", "grow_drop(", "ko_lds_total(", "wit::lds_fits(",
                  '#include "lin_api.h"', "lin_levels(", "lin_sorted_keys("):
         assert name in api, name
-    # the level loop, its buffers' growth and the overflow rule are lin_api.h's, once, for both calls
+    # the level loop, its buffers' growth and the overflow rule are lin_api.h's, once, for all three searches
     drv = open(os.path.join(CSRC, "lin_api.h")).read()
     assert '#include "knock_api.h"' in drv
     for name in ("launch_lin_filter(", "launch_lin_rehash(", "grow_keep(", "lin::cuts_grown(", "lin::emit_grown(", "lin::level_end("):
         assert name in drv, name
-        assert name not in api and name not in api_lin, name
-    assert '#include "lin_api.h"' in api_lin and "lin_levels(" in api_lin and "lin_sorted_keys(" in api_lin
+        assert name not in api and name not in api_lin and name not in api_lrep, name
+    assert "static int lin_levels(" in drv and drv.count("int lin_levels(") == 1
+    # ... and so is the tail of the two searches over one graph, from the tier choice to the rows: its callers name
+    # what differs and neither the level loop nor the keys' way to the host
+    assert "static int lin_node_search(" in drv and drv.count("int lin_node_search(") == 1
+    assert drv.count("lin_levels(c, who,") == 1 and drv.count("lin_sorted_keys(c, b, nullptr,") == 1
+    for src in (api_lin, api_lrep):
+        assert '#include "lin_api.h"' in src and src.count("lin_node_search(c, ls,") == 1
+        assert "lin_levels(" not in src and "lin_sorted_keys(" not in src and "lin::key_unpack(" not in src
     users = [f for f in sorted(os.listdir(CSRC)) if '#include "lin_api.h"' in open(os.path.join(CSRC, f)).read()]
-    assert users == ["api_lgcuts.hip", "api_lineage.hip"]
+    assert users == ["api_lgcuts.hip", "api_lineage.hip", "api_lrepair.hip"]
     host = open(os.path.join(CSRC, "lin_host.h")).read()
     assert "LevelEnd level_end(" in host and "level_end(" not in hdr  # moved, not copied
     ctx = open(os.path.join(CSRC, "ctx.h")).read()

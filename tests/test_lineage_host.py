@@ -111,8 +111,15 @@ def test_host_header_reuses_and_kernels_share_the_need_pass():
     for name in ("k_lin_lds", "k_lin_glob", "k_lin_filter"):
         assert f"void {name}(" in lin, name
     api = open(os.path.join(CSRC, "api_lineage.hip")).read()
-    assert '#include "knock_api.h"' in api and 'GroupTimer timer(c, "k_lineage")' in api and "ensure_nlev(" in api and "ko_lds_total(" in api
-    assert '#include "lin_api.h"' in api and "lin_levels(" in api  # the level loop is the shared driver's
+    assert '#include "knock_api.h"' in api and 'GroupTimer timer(c, "k_lineage")' in api and "ensure_nlev(" in api
+    # the tier choice, the level loop and the rows are the shared tail's: the call names its tier functions and kernels
+    tail = open(os.path.join(CSRC, "lin_api.h")).read()
+    assert '#include "lin_api.h"' in api and "lin_node_search(c, ls," in api and "wit::lds_fits, wit::wit_lds_bytes, wit::glob_words" in api
+    assert '"k_lin_lds"' in api and '"k_lin_glob"' in api and "ls.glob_node_bytes = 32.0" in api
+    for name in ("ko_lds_total(", "c->opt.wit_lds_max", "c->opt.kl_grid", "lin_levels(", "lin_sorted_keys(", "lin::key_unpack("):
+        assert tail.count(name) == 1 + (name in ("lin_levels(", "lin_sorted_keys(")), name  # once (the two: defined, and called once)
+        assert name not in api, name
+    assert "std::function" not in api and "std::function" not in tail
     assert "NEMO_WIT_MASKS" not in api and "nemo_witness_sets(" not in api  # fused: no witness call and a reader
 
 

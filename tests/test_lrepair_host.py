@@ -129,15 +129,40 @@ def test_host_header_reuses_and_kernels_share_the_blame_pass():
     assert "ko_sweep<LDS>(g)" in k and "lin_emit(a, s_key, k, w)" in k and "lin_cut_insert(a, i, k)" in k and "!a.redo" in k
     assert "k_lin_filter" not in k.split("namespace nemo {")[1]  # the filter and the rehash are used as they are
     api = open(os.path.join(CSRC, "api_lrepair.hip")).read()
-    assert '#include "lin_run.h"' in api and "lin_levels_run(" in api and "lin_sorted_run(" in api  # the level loop is lin_api.h's
-    run = open(os.path.join(CSRC, "lin_run.h")).read()
-    api_lin = open(os.path.join(CSRC, "api_lineage.hip")).read()
-    assert "int lin_levels_run(" in run and "int lin_levels_run(" in api_lin and "return lin_levels(" in api_lin
+    # the level loop and the search's tail are lin_api.h's, included directly: no detour through a second header, no
+    # type-erased hook on a per-level path
+    tail = open(os.path.join(CSRC, "lin_api.h")).read()
+    assert '#include "lin_api.h"' in api and "lin_node_search(c, ls," in api and not os.path.exists(os.path.join(CSRC, "lin_run.h"))
+    assert all("lin_run" not in open(os.path.join(CSRC, f)).read() for f in os.listdir(CSRC))
+    assert "std::function" not in api and "std::function" not in tail
     assert "lin::level_end(" not in api and "launch_lin_filter(" not in api  # ... once
-    assert 'GroupTimer timer(c, "k_lrepair")' in api and "ko_lds_total(" in api and "c->opt.wit_lds_max" in api and "c->opt.kl_grid" in api
-    assert "repair::check_lists(" in api and "lrep::status_of_lost(" in api and "cs.rp" not in api and "d_ln" not in api  # its own state
+    assert 'GroupTimer timer(c, "k_lrepair")' in api and "lrep::lds_fits, lrep::lrep_lds_bytes, lrep::glob_words" in api
+    assert '"k_lrep_lds"' in api and '"k_lrep_glob"' in api and "ls.glob_node_bytes = 48.0" in api
+    for name in ("ko_lds_total(", "c->opt.wit_lds_max", "c->opt.kl_grid"):  # the tier code, once, in the tail
+        assert tail.count(name) == 1 and name not in api, name
+    # the absent-set front end is repair_api.h's, once, for the four repair calls, each family on its own state
+    front = open(os.path.join(CSRC, "repair_api.h")).read()
+    api_rep = open(os.path.join(CSRC, "api_repair.hip")).read()
+    for name in ("repair::check_lists(", "repair::bitmap(", "launch_repair_absent(", "launch_lab_hash(", "pairs::plan("):
+        assert front.count(name) == 1 and name not in api and name not in api_rep, name
+    users = [f for f in sorted(os.listdir(CSRC)) if '#include "repair_api.h"' in open(os.path.join(CSRC, f)).read()]
+    assert users == ["api_lrepair.hip", "api_repair.hip"]
+    for src, own in ((api, "cs.lr_abs, cs.d_lrcand, "), (api_rep, "cs.rp_abs, cs.rp.cand, ")):
+        assert src.count("absent_check(c, who,") == 1 and src.count("absent_queue(c, " + own) == 1 and src.count("absent_pair(c, who, " + own) == 1
+    assert "lrep::status_of_lost(" in api and "cs.rp" not in api and "d_ln" not in api and "lr_abs" not in api_rep and "d_lr" not in api_rep  # its own state
     ctx = open(os.path.join(CSRC, "ctx.h")).read()
     assert "LinBufs d_lr;" in ctx and "ev_lrep" in ctx and "h_lrep" in ctx
+    assert ctx.count("struct AbsentSet {") == 1 and "AbsentSet rp_abs;" in ctx and "AbsentSet lr_abs;" in ctx
+    for name in ("rp_bits", "lr_bits", "d_rpcnt", "d_lrcnt", "d_rptab", "d_lrtab", "d_rphreg", "d_lrhreg", "d_rpbits", "d_lrbits"):
+        assert name not in ctx, name
+    # the fetches' copy and its messages: knock_api.h's, once
+    shared = open(os.path.join(CSRC, "knock_api.h")).read()
+    assert shared.count("static inline int fetch_result(") == 1 and shared.count("(or after a later nemo_load_corpus)") == 1
+    assert shared.count('"capacity too small"') == 1
+    for f in ("api_cuts.hip", "api_repair.hip", "api_lineage.hip", "api_lgcuts.hip", "api_lrepair.hip", "cut_api.h", "lin_api.h", "repair_api.h"):
+        src = open(os.path.join(CSRC, f)).read()
+        assert "capacity too small" not in src and "after a later nemo_load_corpus" not in src, f
+        assert ("fetch_result(c, " in src) == f.startswith("api_"), f
 
 
 def test_host_check_program_passes_under_the_host_sanitizers(tmp_path):
